@@ -10,7 +10,13 @@ collectives are the work-partition handshake and the barrier / MAX-reduce of the
 by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or directly: `python bench.py --gpus N`
 starts the N rank processes itself, before anything touches the GPU.
 
-Beside `value` the line carries (every figure ONE timed window of consecutive steps, no best-of-N anywhere):
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) does only what `value` needs: it sets up, runs W untimed steps and
+then more until the timed path has run for --warmup-seconds (3 s), times N steps, writes the last timed step's outputs under
+--dump-outputs DIR, and prints the line.  Its `roofline` holds what the timed window itself yields (HBM against the per-kernel
+HIP events of the timed steps, `valu_issue`).  Everything below that takes runs or checks of its own is measured with --full only.
+
+Beside `value` a --full line carries (every figure ONE timed window of consecutive steps, no best-of-N anywhere):
+  unpipelined         spx_batch_run on one batch, call after call; every buffer set of the timed loop compared with its bytes
   roofline            HBM (the contract's), plus `latency` (walk kernel: cycles per dependent pitch step against the modelled floor)
                       and `valu_fp64` (analysis kernel alone: fp64 operations of the DFT spec per second against the vector peak)
   large_batch         2 048 streams x 10 s in ONE call: the throughput regime, HBM fraction
@@ -25,7 +31,7 @@ Beside `value` the line carries (every figure ONE timed window of consecutive st
   cpu_baseline        the CPU port on the host cores, with the output CRCs of the GPU legs checked against it
   cpu_baseline_fftw   the same with the reference's FFT library when the box has libfftw3 (dlopen); {"fftw": "absent"} otherwise
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  The --no-* options below switch single legs of a --full run off.
 """
 import argparse
 import ctypes as C
@@ -473,6 +479,24 @@ def standalone_analysis_ms(plan, batch, reps=10, warm=3):
     return e0.elapsed_time(e1) / reps
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the per-stream int16 outputs as DIR/out.npy (float32, the streams one after the other) and their lengths
+    as DIR/out_samples.npy (float64).  The headline's 256 streams take 54 MB; should a batch ever exceed 64 MB in all, a fixed
+    seeded sample of its streams is written instead and DIR/out_streams.npy says which (float64 stream indices)."""
+    os.makedirs(path, exist_ok=True)
+    pick = np.arange(len(outs))
+    if sum(o.size for o in outs) * 4 + len(outs) * 16 > DUMP_LIMIT_BYTES:
+        order = np.random.default_rng(0).permutation(len(outs))
+        sizes = np.cumsum([outs[i].size * 4 + 16 for i in order])
+        pick = np.sort(order[:int(np.searchsorted(sizes, DUMP_LIMIT_BYTES - 4096, side="right"))])
+        np.save(os.path.join(path, "out_streams.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "out.npy"), np.concatenate([outs[i].ravel() for i in pick]).astype(np.float32))
+    np.save(os.path.join(path, "out_samples.npy"), np.array([outs[i].size for i in pick], np.float64))
+
+
 def load_scratch_json(name):
     try:
         return json.load(open(os.path.join(ROOT, "gpurun_out", name)))
@@ -494,6 +518,17 @@ def main():
     # inside the timed region -- is 2 % of it and not 5: 100 steps take a tenth of a second)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="also run every other leg and check of the line (unpipelined window, "
+                    "large batch, other rates, PCIe-inclusive pipeline, configs[4], the drop-in API, the CPU baseline, the "
+                    "standalone analysis kernel); without it the run does only what `value` needs")
+    ap.add_argument("--warmup-seconds", type=float, default=None, metavar="S",
+                    help="after the --warmup steps, more untimed steps until the timed path has run for S seconds (default: 3 "
+                         "in a plain run -- 5 steps after an idle GPU read 1.6 %% slower per step over a 20-step window; 0 with "
+                         "--full, whose other legs run first)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed its caller (rank 0's streams) to "
+                         "DIR/out.npy (every stream's output samples one after the other, float32) and DIR/out_samples.npy "
+                         "(output samples per stream, float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie", action="store_true")
     ap.add_argument("--pcie-child", type=str, default=None, metavar="DEV,RANK,REPS",
@@ -519,6 +554,14 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for "
                     "a functional check of the N > 1 path when several ranks share one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.warmup_seconds is None:
+        args.warmup_seconds = 0.0 if args.full else 3.0
+    if not args.full:
+        # a plain run: the headline's set-up, warm-up and timed steps only
+        args.no_pcie = args.no_cpu_baseline = args.no_config4 = args.no_large_batch = args.no_other_rates = args.no_api = True
+        args.no_unpipelined = True
     if args.pcie_child:
         # The PCIe leg in a process of its own, started before the parent touches the GPU (see there).
         import torch
@@ -660,7 +703,7 @@ def main():
 
     # the unpipelined figure (also warms up); --no-unpipelined: profiling runs, whose per-kernel averages should be the timed loop's
     dt_single = None if args.no_unpipelined else time_window(b.run, reps=max(5, args.steps), warm=max(3, args.warmup))
-    if dt_single is None:
+    if dt_single is None and args.full:
         # (the batch whose outputs and chain lengths the line reports; its kernels in sequence: a profiler that serialises kernels
         # must not meet the concurrent mode's polling kernels)
         L.spx_set_concurrent(0)
@@ -670,6 +713,15 @@ def main():
     for k in range(args.warmup):
         step(k)
     barrier()
+    # (each rank on its own clock, synchronising only its device: the ranks meet at the barrier after it)
+    warm_extra, t_w = 0, time.perf_counter()
+    while time.perf_counter() - t_w < args.warmup_seconds:
+        for _ in range(10):
+            step(args.warmup + warm_extra)
+            warm_extra += 1
+        torch.cuda.synchronize()
+    if warm_extra:
+        barrier()
     L.spx_set_timing(1)
     t0 = time.perf_counter()
     for k in range(args.steps):
@@ -686,15 +738,26 @@ def main():
     dt = max_over_ranks(dt)
     n_in = n * STREAMS_PER_GPU
     walk_form = int(L.spx_debug_last_walk_form())
-    outs = b.results()
-    if pipe is not None:   # every buffer set of the pipeline holds the plain call's bytes
-        for t in tickets[-pipe.depth:]:
-            outs2 = pipe.results(t)
-            assert len(outs2) == len(outs) and all(np.array_equal(x, y) for x, y in zip(outs, outs2)), "the batches of the pipelined loop differ"
-            del outs2
+    if pipe is not None:
+        last = pipe.results(tickets[-1])   # what the last timed step handed its caller
+        if args.full:   # every buffer set of the pipeline holds the plain call's bytes
+            outs = b.results()
+            for t in tickets[-pipe.depth:]:
+                outs2 = last if t == tickets[-1] else pipe.results(t)
+                assert len(outs2) == len(outs) and all(np.array_equal(x, y) for x, y in zip(outs, outs2)), "the batches of the pipelined loop differ"
+                del outs2
+        else:
+            outs = last
+        del last
         pipe.close()   # (its streams and buffers go before the other legs run)
+    else:
+        outs = b.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
     n_out = int(sum(o.size for o in outs))
-    chain_steps = b.step_counts()         # pitch searches per stream: the length of every stream's dependent chain
+    # pitch searches per stream: the length of every stream's dependent chain (read from the plain batch, which a plain run
+    # leaves untouched when the timed steps go through the pipeline object)
+    chain_steps = b.step_counts() if (args.full or pipe is None) else None
     if dt_single is not None:
         dt_single = max_over_ranks(dt_single)
     if args.crc_out:
@@ -702,7 +765,7 @@ def main():
             json.dump([zlib.crc32(np.ascontiguousarray(o).tobytes()) for o in outs], f)
 
     # the analysis kernel alone (its fp64 vector roofline), rank 0's device
-    ms_analysis_alone = standalone_analysis_ms(plan, b) if rank == 0 else None
+    ms_analysis_alone = standalone_analysis_ms(plan, b) if rank == 0 and args.full else None
 
     # the throughput regime: 2 048 streams of the headline kind in ONE call (2 048 distinct signals), rank 0's device
     large = None
@@ -871,7 +934,7 @@ def main():
         clock_mhz = float(getattr(torch.cuda.get_device_properties(dev_index), "clock_rate", 2400000)) / 1e3   # nominal shader clock (2 400 MHz)
         lm = load_json("latency_model.json")
         fm = load_json("flop_model.json")
-        smax, smean = int(chain_steps.max()), float(chain_steps.mean())
+        smax, smean = (int(chain_steps.max()), float(chain_steps.mean())) if chain_steps is not None else (0, 0.0)
         latency = None
         if lm and smax > 0 and ms_walk > 0:
             cyc = ms_walk * 1e-3 * clock_mhz * 1e6 / smax
@@ -943,7 +1006,8 @@ def main():
                            {"ms_per_step": dt_single * 1e3, "value": n_in * world / dt_single / 1e6, "unit": "Msamples/s",
                             "note": "spx_batch_run on ONE batch, call after call (its three kernels side by side, the walk "
                                     "waiting for its first speeds at the start of every call); MAX over ranks"},
-            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
+            "warmup": args.warmup, "warmup_extra_steps": warm_extra, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
+            "full": args.full,   # false: the headline alone; the other legs, checks and standalone figures come with --full
             "vs_baseline": None, "dtype": "int16 samples; f64 DFT, f32 features, int32 AMDF/OLA",
             "data": "synthetic",
             "config": {"workload": "BASELINE configs[3]: %d streams/GPU x %d s, 16 kHz mono int16, speed 3.5, "

@@ -2,7 +2,7 @@
 # The evidence of a round's final build, ONE GPU call (gpurun -- bash tools/collect_round.sh TAG): everything lands in
 # gpurun_out/TAG/ ready to be copied into profiles/<round>/ (and pmc_traffic.json / sq_counters.json / perf_reference.json /
 # kernel_resources.json into profiles/):
-#   bench.json, bench_steps20.json          the default bench command and the driver's (--steps 20 --warmup 5)
+#   bench.json, bench_steps20.json          the whole line (--full) and the plain headline run (--steps 20 --warmup 5)
 #   kernel_stats_pipelined_loop.csv         rocprofv3 --kernel-trace --stats of the timed loop (its average launch of the walk
 #                                           kernel must agree with roofline.kernel_ms_per_launch of the line)
 #   pmc_traffic.json                        HBM bytes per launch: --pmc FETCH_SIZE / WRITE_SIZE, separate passes, kernels in sequence
@@ -17,17 +17,17 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 OUT=$PWD/gpurun_out; D=$OUT/$TAG; mkdir -p "$D"
 Q="--no-cpu-baseline --no-pcie --no-api --no-config4 --no-large-batch --no-other-rates"
 if has bench; then
-python3 bench.py > "$D/bench.json" 2> "$D/bench.err"; echo "bench rc $?"; head -c 600 "$D/bench.json"; echo
+python3 bench.py --full > "$D/bench.json" 2> "$D/bench.err"; echo "bench rc $?"; head -c 600 "$D/bench.json"; echo
 python3 bench.py --steps 20 --warmup 5 > "$D/bench_steps20.json" 2>> "$D/bench.err"; echo "bench steps20 rc $?"
 fi
 if has stats; then
-timeout 600 rocprofv3 --kernel-trace --stats -d "$D/stats" -o stats --output-format csv -- python3 bench.py $Q --no-unpipelined > "$D/stats.log" 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d "$D/stats" -o stats --output-format csv -- python3 bench.py --full $Q --no-unpipelined > "$D/stats.log" 2>&1
 cp $(find "$D/stats" -name "*kernel_stats.csv" | head -1) "$D/kernel_stats_pipelined_loop.csv" 2>/dev/null; head -6 "$D/kernel_stats_pipelined_loop.csv"
 fi
 if has pmc; then
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --kernel-trace --pmc $c -d "$D/dir_pmc_$c" -o pmc --output-format csv -- python3 bench.py --serial --steps 3 --warmup 1 $Q > "$D/pmc_$c.log" 2>&1
-  timeout 600 rocprofv3 --kernel-trace --pmc $c -d "$D/dir_pmcp_$c" -o pmc --output-format csv -- python3 bench.py --steps 3 --warmup 1 $Q --no-unpipelined > "$D/pmcp_$c.log" 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $c -d "$D/dir_pmc_$c" -o pmc --output-format csv -- python3 bench.py --full --serial --steps 3 --warmup 1 $Q > "$D/pmc_$c.log" 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $c -d "$D/dir_pmcp_$c" -o pmc --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 $Q --no-unpipelined > "$D/pmcp_$c.log" 2>&1
 done
 fi
 has sq && { bash tools/sq_counters.sh $TAG/sq > "$D/sq.log" 2>&1; cp "$OUT/$TAG/sq_sq_counters.json" "$D/sq_counters.json" 2>/dev/null; rm -f "$OUT/$TAG/sq_sq_counters.json"; }
