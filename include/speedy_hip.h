@@ -280,7 +280,7 @@ long long spx_debug_arith_check(unsigned seed, unsigned threads, unsigned per_th
 int spx_debug_log_check(unsigned first_block, unsigned end_block, unsigned long long* sums);
 /* Diagnostics: 1 if the last spx_batch_run / analyze+walk call of this process took the concurrent three-kernel mode, 2 if it was
  * pipelined with the previous call (spx_batch_run_ahead), 0 if it launched its kernels in sequence (another process holds the
- * device's concurrent-mode lock, a tuning variable, the batch shape). */
+ * device's concurrent-mode lock, spx_set_concurrent(0), the batch shape). */
 int spx_debug_last_call_concurrent(void);
 /* Sum over the same calls of the frame-rate (tension) kernel's time, as of the last spx_timing_collect. */
 double spx_timing_last_tension_ms(void);

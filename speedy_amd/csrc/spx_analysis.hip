@@ -78,8 +78,6 @@ static __host__ __device__ inline size_t work_bytes(int W, int tf, bool ct = fal
 // 16 kHz (W = 240 = 4*4*3*5) and 22.05 kHz (W = 330 = 2*3*5*11) have their own instantiations of the kernel; every
 // other window size takes the plan-driven one.  Returns the compiled-in window size, or 0.
 static inline int plan_ct_window(const SpxPlanDev& P) {
-  static const bool generic_only = spx_tuning_env("SPX_ANALYSIS_GENERIC") != nullptr;  // A/B and tests of the plan-driven path
-  if (generic_only) return 0;
   auto is = [](const int* r, int n, std::initializer_list<int> want) {
     if (n != (int)want.size()) return false;
     int k = 0;
@@ -118,9 +116,7 @@ static size_t analysis_lds_bytes(const SpxPlanDev& P, bool ct) {  // for the til
   size_t mags = (size_t)(tf + 1) * spx_mag_stride(P.W) * sizeof(float);
   size_t small = (size_t)3 * (tf + 1) * sizeof(float);
   size_t stage = (stage_samples(P, tf) * sizeof(short) + 15) & ~(size_t)15;
-  // tuning only (fewer workgroups per CU); part of the size so that the co-residency rule sees it; read once per process
-  static const size_t pad = [] { const char* e = spx_tuning_env("SPX_ANALYSIS_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();
-  return work_bytes(P.W, tf, ct, P.dft_waves) + ((mags + 15) & ~(size_t)15) + ((small + 15) & ~(size_t)15) + stage + pad;
+  return work_bytes(P.W, tf, ct, P.dft_waves) + ((mags + 15) & ~(size_t)15) + ((small + 15) & ~(size_t)15) + stage;
 }
 // what spx_launch_analysis (int16 input) will ask for: the engine's co-residency arithmetic uses this
 size_t spx_analysis_lds_bytes(const SpxPlanDev& P) { return analysis_lds_bytes(P, plan_ct_window(P) != 0); }

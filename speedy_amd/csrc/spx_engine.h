@@ -67,11 +67,7 @@ struct SpxRange {
 #define SPX_MAX_CHUNKS 16
 // The plan's ring of earlier calls (ring_wait below) and the library's walk streams per device (dev_walk_streams): the walk kernels
 // of consecutive pipelined calls take turns on up to SPX_MAX_WALK_STREAMS streams, and the ring remembers twice as many calls.
-#ifdef SPX_TUNING
-#define SPX_MAX_WALK_STREAMS 8   // (the developers' build: up to eight walk launches in flight, SPX_WALK_STREAMS)
-#else
 #define SPX_MAX_WALK_STREAMS 4
-#endif
 #define SPX_RING (2 * SPX_MAX_WALK_STREAMS)
 // Pinned staging slot for the small host tables of a call (job tables, tile order): the async copies read it after the
 // call has returned, so it is plan-owned and reused only once its copies have retired.
@@ -97,10 +93,8 @@ struct spx_plan {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [mode][begin / end]
   } trial;
   std::map<long long, SpxModeResources> res_cache;   // mode_resources: per batch shape
-  // spx_batch_run of more streams than CUs, split into overlapping sub-batches (run_split): the event its sub-batches' producers
-  // wait for (two, taking turns), and how the call that last used a workspace was split (spx_batch_read_steps must find the states)
-  hipEvent_t ev_split[2] = {nullptr, nullptr};
-  unsigned split_calls = 0;
+  // an overlapped call of more streams than CUs, split into overlapping sub-batches (run_split): how the call that last used a
+  // workspace was split (spx_batch_read_steps must find the states)
   std::map<const void*, int> split_of;
   void* tables = nullptr;  // one device allocation behind dev.tw/tw2/window/taper*
   // time-chunk pipelining of one batch call: the analysis of chunk c+1 runs on `side` while the walk of chunk c

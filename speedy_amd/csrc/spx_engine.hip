@@ -153,10 +153,6 @@ static int build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n,
     for (int c = 0; c < nch; c++) {
       int64_t n_c = j.n_in;
       if (c < nch - 1) n_c = (j.n_in * (c + 1) / nch) / d.B * d.B;
-#ifdef SPX_TUNING
-      static const int frac = [] { const char* e = getenv("SPX_CHUNK_FRAC"); return e ? atoi(e) : 0; }();   // A/B: the first of two chunks, percent
-      if (frac > 0 && nch == 2 && c == 0) n_c = (j.n_in * frac / 100) / d.B * d.B;
-#endif
       SpxStreamDev& s = v[(size_t)c * n + i];
       s.in_off = j.in_off; s.n_in = n_c; s.out_off = j.out_off; s.out_cap = j.out_cap;
       s.channels = j.channels; s.speed = j.speed; s.nonlinear = j.nonlinear; s.feedback = j.feedback;
@@ -246,18 +242,10 @@ int dev_side_streams(int dev, hipStream_t* side, hipStream_t* side2) {
 }
 
 // The walk kernels of consecutive pipelined calls take turns on streams of the library's (run_impl): the device's SECOND side
-// stream -- idle in that order: the tension kernel runs behind the analysis on the first -- and up to three more.  Round 4 ran two
-// (four streams per device in all, the caller's included: one per hardware queue of HIP's default four); since round 5 the library
-// asks for eight hardware queues, and round 6 lets the mode decide how many walk launches are in flight (walk_stream_count).
-int walk_stream_count() {
-  static const int n = [] {
-    const char* e = spx_tuning_env("SPX_WALK_STREAMS");
-    if (!e && spx_tuning_env("SPX_WALK_STREAMS3")) return 3;
-    const int v = e ? atoi(e) : 2;
-    return v < 1 ? 1 : (v > SPX_MAX_WALK_STREAMS ? SPX_MAX_WALK_STREAMS : v);
-  }();
-  return n;
-}
+// stream -- idle in that order: the tension kernel runs behind the analysis on the first -- and one more: two walk launches in flight
+// (four streams per device in all, the caller's included: one per hardware queue of HIP's default four; more walk streams did not
+// shorten the step, profiles/r06).  Mixed calls take up to SPX_MAX_WALK_STREAMS (spx_mixed.hip).
+int walk_stream_count() { return 2; }
 int dev_walk_streams(int dev, hipStream_t* w, int n) {
   static std::mutex mu;
   static hipStream_t s3[64][SPX_MAX_WALK_STREAMS];   // [.][0] unused: the first walk stream is the second side stream
@@ -330,21 +318,7 @@ int ring_record(spx_plan* plan, hipStream_t on, void* ws, hipStream_t st, const 
 
 // ---- the inputs of spx_choose_mode (spx_mode.h) ----
 SpxModeEnv mode_env() {
-  // the developers' A/B switches exist in builds with -DSPX_TUNING only (spx_tuning_env); read once per process
-  static const SpxModeEnv fixed = [] {
-    SpxModeEnv e;
-    memset(&e, 0, sizeof(e));
-    e.serial = spx_tuning_env("SPX_SERIAL") != nullptr;             // kernels back to back on one stream
-    e.no_lean = spx_tuning_env("SPX_NO_LEAN_WALK") != nullptr;
-    e.small_tile = spx_tuning_env("SPX_TILE_SMALL") != nullptr;     // the 8-frame tile whenever concurrent
-    e.ahead_any = spx_tuning_env("SPX_AHEAD_ANY") != nullptr;       // the pipelined order whatever the co-residency arithmetic says
-    e.full_walk = spx_tuning_env("SPX_OVERLAP_FULL_WALK") != nullptr;   // overlapped calls keep the full walk form
-    e.walk1 = spx_tuning_env("SPX_AHEAD_WALK1") != nullptr;         // pipelined calls' walk kernels on the caller's stream, one after the other
-    e.no_excl = spx_tuning_env("SPX_NO_EXCLUSIVE_CU") != nullptr;
-    e.trial_force = spx_tuning_env("SPX_TRIAL_FORCE") ? atoi(spx_tuning_env("SPX_TRIAL_FORCE")) : -1;
-    return e;
-  }();
-  SpxModeEnv e = fixed;
+  SpxModeEnv e;
   e.concurrent_enabled = g_concurrent.load() != 0;
   e.chunks_set = g_chunks_set.load();
   e.chunks = g_chunks.load();
@@ -370,10 +344,6 @@ SpxModeWalk mode_walk(const SpxPlanDev& d, int n, int maxC, bool speedup_only, b
   w.lds = c.lds; w.waves = c.waves; w.fast_kernel = c.fast_kernel; w.nwc = c.nwc;
   w.vgprs = spx_walk_vgprs(d, n, maxC, speedup_only, lean, any_speed, short_window);
   return w;
-}
-static bool mixed_long_window_env() {   // A/B (tuning build): overlapped mixed calls keep the 8192-frame window
-  static const bool v = spx_tuning_env("SPX_MIXED_LONG_WINDOW") != nullptr;
-  return v;
 }
 // (cached per plan and shape: the register queries and spx_walk_config are not free, and the engine asks on every call)
 // (short_window: the walk kernel as an overlapped mixed call launches it -- SpxForce::no_exclusive)
@@ -501,7 +471,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   //     object: 1.33 -> 1.21 ms per batch): at the LAUNCH only -- the arithmetic stays with the long window's numbers, which errs on
   //     the safe side (less LDS than counted) and leaves every decision where it was (done with the short window's, 22.05 kHz stereo
   //     turns "doubtful", goes to the timed trial and ends in the concurrent mode: 1.69 -> 2.9 ms through the pipeline object).
-  const bool short_window_res = opt.force && opt.force->no_exclusive && !mixed_long_window_env();
+  const bool short_window_res = opt.force && opt.force->no_exclusive;
   const SpxModeResources& R = mode_resources(plan, n, maxC, speedup_only, any_speed, short_window_res);
   if (R.walk.lds > 160 * 1024)   // one CU's LDS; the window holds every channel of maxRequired + 64 frames at least
     return fail(-1, "spx_batch: too many channels for the walk kernel's LDS window");
@@ -633,8 +603,6 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   // (Round 5 tried staging a DETACHED call's tables on its own, otherwise empty, run stream -- beside the previous call's producers
   // instead of in front of this call's on the producers' stream: 1.045 against 0.94 ms per step.  A stream that holds nothing but
   // waits and one small kernel is exactly the "blocked barrier packets" case of INTEGRATION.md's hardware-queue section.)
-  static const bool no_gate = spx_tuning_env("SPX_NO_GATE") != nullptr;  // A/B only
-  static const bool split_gate = spx_tuning_env("SPX_SPLIT_GATE") != nullptr;  // A/B only: the pipelined call's gate as a kernel of its own
   // AHEAD: the analysis must not fill the CUs before the PREVIOUS call's walk workgroups have been placed one per CU (its walk
   // kernel becomes runnable at the same moment as this analysis: when the walk before it retires) -- only while that call is
   // still in flight (then its workspace, where the counter lives, is alive by the usual contract), and not when the producers
@@ -644,11 +612,11 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   // itself be waiting for something of the caller's (an output buffer still being copied out), and a gate that gives up early
   // lets this call's analysis fill the CUs first, which costs the previous call half its speed; ~2 ms.  The gate runs at the end of
   // the staging kernel (same stream, nothing in between).
-  const bool ahead_gate = ahead && !force && plan->ahead_started != nullptr && plan->ahead_n > 0 && !no_gate && !waited_prev &&
+  const bool ahead_gate = ahead && !force && plan->ahead_started != nullptr && plan->ahead_n > 0 && !waited_prev &&
                           ring_previous_in_flight(plan);
   rc = stage_tables(plan, sv, order, dstreams, d_order, d_flags, concurrent ? (unsigned)tiles[0] : 0u, d_ready,
                     (concurrent || ahead) ? (unsigned)n + 1u : 0u, (ahead || chunk_ahead) ? sa : st, &staged_ev,
-                    (ahead_gate && !split_gate) ? plan->ahead_started : nullptr, plan->ahead_n, 8000u);
+                    ahead_gate ? plan->ahead_started : nullptr, plan->ahead_n, 8000u);
   if (rc) return rc;
   if (M.trial_slot >= 0) {  // bracket this call on the caller's stream (spx_plan::Trial)
     hipEvent_t& e0 = TR.ev[2 * M.trial_slot];
@@ -662,9 +630,6 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
     HIPCHK(hipStreamWaitEvent(sa, staged_ev, 0));
     if (concurrent) HIPCHK(hipStreamWaitEvent(plan->side2, staged_ev, 0));
   }
-  static const unsigned gate_spins = [] { const char* e = spx_tuning_env("SPX_GATE_SPINS"); return e ? (unsigned)atoi(e) : 1200u; }();
-  static const bool diag_nowait = spx_tuning_env("SPX_DIAG_NOWAIT") != nullptr;  // DIAGNOSTIC ONLY: the walk reads the speeds the
-  // previous identical call left in the scratch array instead of waiting for this call's (timing experiments)
   for (int c = 0; c < nch; c++) {
     SpxStreamDev* dj = dstreams + (size_t)c * n;
     // Concurrent mode on an IDLE device (the first call after a synchronisation): kernels start as their launches arrive, and the
@@ -675,10 +640,8 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
     // producers queued behind a waiting consumer in a shared queue never start (every consumer is enqueued after its producers,
     // which is safe with any mapping).  So an idle start holds the analysis stream back with a gate kernel until the walk kernel's
     // workgroups have been placed (they count themselves in; spx_gate_kernel).
-    if (concurrent && do_w && idle_start && !no_gate)
-      hipLaunchKernelGGL(spx_gate_kernel, dim3(1), dim3(64), 0, sa, d_ready + n, n, gate_spins);
-    if (ahead_gate && split_gate && c == 0)
-      hipLaunchKernelGGL(spx_gate_kernel, dim3(1), dim3(64), 0, sa, plan->ahead_started, plan->ahead_n, 8000u);
+    if (concurrent && do_w && idle_start)
+      hipLaunchKernelGGL(spx_gate_kernel, dim3(1), dim3(64), 0, sa, d_ready + n, n, 1200u);
     if (do_a && tiles[c] > 0) {
       SpxTimed tm(timed, 0, sa);
       spx_launch_analysis(d, dj, n, tiles[c], in, rec, td, concurrent ? d_order : nullptr, concurrent ? d_flags : nullptr, sa);
@@ -705,9 +668,9 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
         // AHEAD: the counts are all published by the time the kernel starts -- its one poll returns at once -- and its workgroups
         // count themselves in for the next call's gate.
         SpxTimed tm(timed, 1, stw);
-        spx_launch_walk(d, dj, n, maxC, in, out, n_out, states, scratch, ((concurrent && !diag_nowait) || ahead) ? d_ready : nullptr,
+        spx_launch_walk(d, dj, n, maxC, in, out, n_out, states, scratch, (concurrent || ahead) ? d_ready : nullptr,
                         speedup_only, stw, false, (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, M.launch_lean, any_speed,
-                        short_window_res || (!force && M.walk2 && !M.launch_lean && maxC > 1 && !mixed_long_window_env()));
+                        short_window_res || (!force && M.walk2 && !M.launch_lean && maxC > 1));
       }
       if (M.ahead_forced && force->started_out) *force->started_out = d_ready + n;
       if (c == nch - 1 && !force) {
@@ -754,7 +717,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
 // sub-batch's producers must wait for the caller's stream as it stood at the call and nothing of the NEXT call can start before
 // this call's last walk kernel ends -- 512 streams 3.21 ms split against 2.85 as one call, 1 024 streams 5.63 against 4.34 (the
 // throughput-form walk kernel).  Above two streams per CU the throughput form wins in every order (1 024 streams: four
-// overlapped 256-stream calls 4.8 ms).  (SPX_SPLIT_PLAIN / SPX_SPLIT_MAX in the tuning build: the A/B.)
+// overlapped 256-stream calls 4.8 ms).
 #define SPX_SPLIT_LIMIT 4   // sub-batches the workspace is sized for
 struct SplitPlan { int k; std::vector<int> first; std::vector<size_t> ws_off, ws_bytes; size_t total; };
 static SplitPlan split_geometry(const spx_plan* plan, const spx_stream_job* jobs, int n, int max_mult) {
@@ -779,10 +742,7 @@ static SplitPlan split_geometry(const spx_plan* plan, const spx_stream_job* jobs
 static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out, void* ws,
                      size_t ws_bytes, const spx_taps* taps, void* hs, const SpxCallOpts& opt) {
   if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
-  static const int max_overlapped = [] { const char* e = spx_tuning_env("SPX_SPLIT_MAX"); return e ? atoi(e) : 2; }();
-  static const int max_plain = [] { const char* e = spx_tuning_env("SPX_SPLIT_PLAIN"); return e ? atoi(e) : 1; }();
-  const bool plain = !opt.ahead_req;
-  SplitPlan P = split_geometry(plan, jobs, n, plain ? max_plain : (opt.overlap_req ? max_overlapped : 1));
+  SplitPlan P = split_geometry(plan, jobs, n, opt.ahead_req && opt.overlap_req ? 2 : 1);
   if (P.k > 1 && (g_chunks_set.load() || ws_bytes < P.total)) P.k = 1;
   if (P.k > 1) {
     // would a sub-batch take the pipelined order with overlapping walk kernels?
@@ -806,18 +766,6 @@ static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
   }
   if (P.k <= 1) return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, opt);
   { std::lock_guard<std::mutex> g(plan->mu); if (plan->split_of.size() > 64) plan->split_of.clear(); plan->split_of[ws] = P.k; }
-  hipStream_t st = static_cast<hipStream_t>(hs);
-  void* ready = opt.in_ready;
-  if (plain) {
-    // plain stream order: every sub-batch's producers wait for the caller's stream as it stands now (one event per call in
-    // flight would be the exact thing; two taking turns are enough: the event is waited for by the sub-batches' producer
-    // streams, and those are ordered behind the previous split call's by the ring)
-    std::lock_guard<std::mutex> g(plan->mu);
-    hipEvent_t& e = plan->ev_split[plan->split_calls++ & 1];
-    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(e, st));
-    ready = e;
-  }
   int64_t rows = 0;
   for (int i = 0; i < P.k; i++) {
     const int a = P.first[i], m = P.first[i + 1] - a;
@@ -834,8 +782,8 @@ static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
     SpxCallOpts o;
     o.ahead_req = o.overlap_req = true;
     o.split_part = true;
-    o.sub = i > 0 || plain;      // (the first sub-batch of an overlapped call is ordered like the call itself: "the same out buffer again")
-    o.in_ready = ready;
+    o.sub = i > 0;      // (the first sub-batch of an overlapped call is ordered like the call itself: "the same out buffer again")
+    o.in_ready = opt.in_ready;
     if (i == P.k - 1) o.done_event = opt.done_event;   // (on hip_stream, which waits for every sub-batch's walk kernel: never detached)
     const int rc = run_impl(plan, jobs + a, m, in, out, n_out + a, static_cast<unsigned char*>(ws) + P.ws_off[i], P.ws_bytes[i],
                             taps ? &t : nullptr, hs, true, true, o);

@@ -5,15 +5,9 @@
 
 #include <stdlib.h>
 
-// A/B switches of the developers' tools (tools/ab_lib.sh, tools/scale_sweep.sh ...) exist only in builds with -DSPX_TUNING
-// (`make -C speedy_amd/csrc tuning` -> speedy_amd/lib/ab/libspeedy_hip_tuning.so).  The shipped library reads the documented
-// environment variables only (INTEGRATION.md "Environment"): SPX_NO_POOL, SPX_POOL_*, SPX_SHARED_GPU, SPX_LOCK_DIR,
-// SPX_DEBUG_MODE, SPX_DEBUG_TRIAL.
-#ifdef SPX_TUNING
-static inline const char* spx_tuning_env(const char* name) { return getenv(name); }
-#else
-static inline const char* spx_tuning_env(const char*) { return nullptr; }
-#endif
+// The library reads the documented environment variables only (INTEGRATION.md "Environment"): SPX_NO_POOL, SPX_POOL_*,
+// SPX_SHARED_GPU, SPX_LOCK_DIR, SPX_DEBUG_MODE, SPX_DEBUG_TRIAL, SPX_KEEP_HW_QUEUES and GPU_MAX_HW_QUEUES.  Variants are
+// compile-time (-DSPX_WALK_PAD=n, -DSPX_STAMPS, SPX_HOT_SCHED: tools/build_variant.sh).
 
 // Speeds the speed-up walk kernel (spx_walk_fast.hip) serves: its division for the step lengths is the IEEE sequence without
 // the scaling half, exact for speed - 1 in [2^-60, 2^80) (fast_div).  Anything beyond (a speed of 1e18 turns every step into a

@@ -108,15 +108,13 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     G.push_back(mg);
   }
   const int groups = (int)G.size();
-  static const int env_mixed = spx_tuning_env("SPX_MIXED_MODE") ? atoi(spx_tuning_env("SPX_MIXED_MODE")) : -1;   // tuning: 0 sequence, 1 concurrent
-  static const bool no_sjf = spx_tuning_env("SPX_MIXED_NO_ORDER") != nullptr;   // A/B
   SpxModeRuntime T;
   memset(&T, 0, sizeof(T));
   T.device_ours = device_ours_cb;
   T.device_ctx = &lead->device;
   const SpxModeEnv E = mode_env();
   SpxMixedMode MM = spx_choose_mixed_mode(G.data(), groups, n, lead->cu_count, lead->lds_per_cu, spx_tension_lds_bytes(), spx_tension_vgprs(),
-                                          E, env_mixed, no_sjf, ahead_req, T);
+                                          E, ahead_req, T);
   // ---- the device guard, once for the whole call ----
   SpxDevGuard& guard = g_guard[(lead->device >= 0 && lead->device < 64) ? lead->device : 0];
   std::unique_lock<std::mutex> guard_lock(guard.mu, std::defer_lock);
@@ -129,7 +127,7 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     if (guard.valid && guard.last_stream != st && q == hipErrorNotReady) {
       T.guard_busy = true;
       MM = spx_choose_mixed_mode(G.data(), groups, n, lead->cu_count, lead->lds_per_cu, spx_tension_lds_bytes(), spx_tension_vgprs(), E,
-                                 env_mixed, no_sjf, ahead_req, T);
+                                 ahead_req, T);
       guard_lock.unlock();
     }
   }
@@ -142,8 +140,7 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
   // walk streams -- two pairs taking turns, so at most two calls' walk kernels are in flight --, their workgroups without the LDS
   // request that gives each a CU of its own (two calls' workgroups share the CUs), the scatter kernel and the call's events behind
   // them on the first group's walk stream, nothing on the caller's.  configs[4] shard: 1.87 - 1.97 -> see profiles/r06.
-  static const bool no_mixed_walk2 = spx_tuning_env("SPX_MIXED_NO_WALK2") != nullptr;   // A/B
-  const bool walk2 = spx_mixed_walk2(MM, detached_req, taps != nullptr, E) && !no_mixed_walk2;
+  const bool walk2 = spx_mixed_walk2(MM, detached_req, taps != nullptr);
   static_assert(SPX_MAX_WALK_STREAMS >= 4, "two pairs of walk streams taking turns");
   hipStream_t wst[SPX_MAX_WALK_STREAMS] = {nullptr};
   if (walk2 && dev_walk_streams(lead->device, wst, 4)) return fail(-1, "spx_batch_run_mixed: no walk streams");

@@ -43,12 +43,10 @@ struct SpxModeShape {
   bool ahead_req;           // spx_batch_run_ahead / _overlapped / the pipeline object
   bool overlap_req;         // spx_batch_run_overlapped: the walk kernels of consecutive calls may overlap
 };
-struct SpxModeEnv {         // process-wide settings (spx_set_*) and the developers' A/B switches (all false in the shipped library)
+struct SpxModeEnv {         // process-wide settings (spx_set_*)
   bool concurrent_enabled;  // spx_set_concurrent
   bool chunks_set;          // spx_set_pipeline_chunks was called
   int chunks;
-  bool serial, no_lean, small_tile, ahead_any, full_walk, walk1, no_excl;
-  int trial_force;          // -1: trials decide; 0 / 1: no trial
 };
 struct SpxModeTrial {       // plan-owned state of the timed trial of "doubtful" shapes (one analysis wave per SIMD beside the consumers)
   long long key;
@@ -106,7 +104,6 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
   if (per_stream_lds + 2 * R.an_lds_default > lds_usable && both && R.tile_default == R.tile_big &&
       per_stream_lds + 2 * R.an_lds_small <= lds_usable)
     tile = R.tile_small;
-  if (E.small_tile && both && tile == R.tile_big) tile = R.tile_small;
   const size_t an_lds = tile == R.tile_default ? R.an_lds_default : R.an_lds_small;
   const int an_vgprs = tile == R.tile_default ? R.an_vgprs_default : R.an_vgprs_small;
   // rule 1 (deadlock freedom) and rule 2 (worth it)
@@ -128,9 +125,9 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
   // the trial of doubtful shapes: first call concurrent and untimed (cold), second concurrent and timed, third in sequence and
   // timed, later calls take the faster
   int trial_slot = -1;
-  if (co_resident && doubtful && both && E.concurrent_enabled && !E.serial && !S.forced) {
+  if (co_resident && doubtful && both && E.concurrent_enabled && !S.forced) {
     SpxModeTrial& N = M.trial_next;
-    if (N.key != T.trial_key) { N.key = T.trial_key; N.calls = 0; N.choice = E.trial_force; }
+    if (N.key != T.trial_key) { N.key = T.trial_key; N.calls = 0; N.choice = -1; }
     if (N.choice < 0 && N.calls >= 3 && T.trial_times_ready) N.choice = T.ms_con < T.ms_seq ? 1 : 0;
     if (N.choice >= 0) co_resident = N.choice == 1;
     else if (N.calls == 0) { }
@@ -141,7 +138,7 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
   }
   M.co_resident = co_resident;
   M.trial_slot = trial_slot;
-  bool want_concurrent = E.concurrent_enabled && !E.serial && co_resident && both;
+  bool want_concurrent = E.concurrent_enabled && co_resident && both;
   if (want_concurrent && !S.forced && !ours()) want_concurrent = false;   // another process works on this GPU
   if (S.forced) want_concurrent = S.force_concurrent && both;
   M.ahead_forced = S.forced && S.force_ahead && both;
@@ -149,7 +146,7 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
   // a batch whose kernels run in sequence can still be pipelined with its predecessor if ONE analysis workgroup fits beside a
   // walk workgroup that asks for a CU of its own and one analysis wave beside its waves (default tile, full walk form)
   bool seq_ahead = false;
-  if (S.ahead_req && !want_concurrent && !S.forced && both && S.n <= R.cu_count && E.concurrent_enabled && !E.serial &&
+  if (S.ahead_req && !want_concurrent && !S.forced && both && S.n <= R.cu_count && E.concurrent_enabled &&
       trial_slot < 0 && chunks_free && !lean_walk) {
     const size_t walk_lds = W.lds > R.lds_per_cu / 2 + 1024 ? W.lds : R.lds_per_cu / 2 + 1024;
     const int walk_regs = ((W.waves + 3) / 4) * W.vgprs;
@@ -158,8 +155,7 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
   }
   M.seq_ahead = seq_ahead;
   M.ahead = M.ahead_forced || seq_ahead ||
-            (S.ahead_req && (want_concurrent || (E.ahead_any && both && S.n <= R.cu_count && E.concurrent_enabled)) && !doubtful &&
-             !S.forced && trial_slot < 0 && chunks_free);
+            (S.ahead_req && want_concurrent && !doubtful && !S.forced && trial_slot < 0 && chunks_free);
   // a batch without a single analysis frame (linear jobs only: the TSM stage alone) has no producers to run ahead of anything: its
   // walk kernel on the caller's stream, call after call (measured, profiles/r05/r5k_scale_configs.txt: 16 kHz linear 0.5x 2.86 ms
   // plain against 3.55 in the pipelined order)
@@ -176,9 +172,9 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
   if (nch > SPX_MODE_MAX_CHUNKS) nch = SPX_MODE_MAX_CHUNKS;
   M.nch = nch;
   M.concurrent = want_concurrent && nch == 1 && S.has_frames;
-  M.walk2 = S.overlap_req && !E.walk1 && M.ahead && !S.forced && !seq_ahead;
+  M.walk2 = S.overlap_req && M.ahead && !S.forced && !seq_ahead;
   const int total = S.forced ? S.force_total_streams : S.n;
-  M.exclusive_cu = !M.concurrent && (!M.ahead || M.ahead_forced || seq_ahead) && !E.no_excl && nch == 1 && total <= R.cu_count;
+  M.exclusive_cu = !M.concurrent && (!M.ahead || M.ahead_forced || seq_ahead) && nch == 1 && total <= R.cu_count;
   M.launch_lean = lean_walk && (M.concurrent || M.ahead);
   // Large calls asked to be pipelined (spx_batch_run_ahead / _overlapped, the pipeline object): kernels in sequence, two time chunks --
   // the analysis chunks on the side stream, the tension and walk kernels on the caller's behind them.  With the producers started at
@@ -186,7 +182,7 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
   // after call, beside the walk chunks on the caller's stream: the period of back-to-back calls is the larger of the two kernel sums
   // instead of their overlap-less tail and head added up.
   M.chunk_ahead = S.ahead_req && !S.forced && both && !M.ahead && !want_concurrent && nch >= 2 && S.n > 2 * R.cu_count &&
-                  E.concurrent_enabled && !E.serial && trial_slot < 0 && ours();
+                  E.concurrent_enabled && trial_slot < 0 && ours();
   return M;
 }
 
@@ -201,11 +197,11 @@ static inline SpxMode spx_choose_mode(const SpxModeShape& S, const SpxModeResour
                                       const SpxModeTrial& trial_in) {
   const size_t lds_usable = R.lds_per_cu > 6144 ? R.lds_per_cu - 6144 : R.lds_per_cu;
   const bool lean_possible = S.do_a && S.do_w && S.max_channels == 1 && S.n <= R.cu_count && R.walk.fast_kernel && R.walk.nwc > 0 &&
-                             !E.no_lean && !S.forced && R.lean_valid && R.walk_lean.fast_kernel && R.walk_lean.nwc == 0;
+                             !S.forced && R.lean_valid && R.walk_lean.fast_kernel && R.walk_lean.nwc == 0;
   const bool lean_fits = lean_possible && spx_mode_fits2(R, R.walk_lean, lds_usable);
   const bool need_lean = lean_fits && !spx_mode_fits2(R, R.walk, lds_usable);
   SpxMode M = spx_mode_pass(S, R, E, T, trial_in, need_lean);
-  if (!need_lean && lean_fits && M.walk2 && S.overlap_req && !E.full_walk && !T.two_workspaces) {
+  if (!need_lean && lean_fits && M.walk2 && S.overlap_req && !T.two_workspaces) {
     SpxMode L = spx_mode_pass(S, R, E, T, trial_in, true);
     L.asked_device = L.asked_device || M.asked_device;
     if (L.ahead && L.walk2) return L;
@@ -228,8 +224,8 @@ struct SpxMixedMode {
   bool asked_device;
 };
 static inline SpxMixedMode spx_choose_mixed_mode(const SpxModeGroup* G, int groups, int n_total, int cu_count, size_t lds_per_cu,
-                                                 size_t tension_lds, int tension_vgprs, const SpxModeEnv& E, int env_mixed_mode,
-                                                 bool no_order, bool ahead_req, const SpxModeRuntime& T) {
+                                                 size_t tension_lds, int tension_vgprs, const SpxModeEnv& E, bool ahead_req,
+                                                 const SpxModeRuntime& T) {
   SpxMixedMode M = {false, false, false, false};
   size_t cons_lds = 0, cons_waves = 0, max_ps_lds = 0, max_an_lds = 0;
   int max_walk_regs = 0, max_an_regs = 0;
@@ -254,13 +250,12 @@ static inline SpxMixedMode spx_choose_mixed_mode(const SpxModeGroup* G, int grou
     if (max_ps_lds + 2 * max_an_lds > lds_usable) concurrent = false;
     if (max_walk_regs + tension_vgprs + 2 * max_an_regs > 512) concurrent = false;
   }
-  if (!E.concurrent_enabled || E.serial || groups == 0) concurrent = false;
-  if (env_mixed_mode >= 0 && max_an_lds > 0) concurrent = env_mixed_mode == 1;
+  if (!E.concurrent_enabled || groups == 0) concurrent = false;
   if (concurrent && !ours()) concurrent = false;
   if (concurrent && T.guard_busy) concurrent = false;   // (before `ahead`: a call that hits the busy guard is still pipelined -- ADVICE r5)
-  M.ahead = ahead_req && !concurrent && E.concurrent_enabled && !E.serial && groups > 0 && n_total <= cu_count && ours();
+  M.ahead = ahead_req && !concurrent && E.concurrent_enabled && groups > 0 && n_total <= cu_count && ours();
   M.concurrent = concurrent;
-  M.chain_analyses = !concurrent && !no_order && groups > 1;
+  M.chain_analyses = !concurrent && groups > 1;
   return M;
 }
 
@@ -269,8 +264,8 @@ static inline SpxMixedMode spx_choose_mixed_mode(const SpxModeGroup* G, int grou
 // device -- and hands over no taps.  Its first two groups' walk kernels then go to the library's walk streams, two pairs taking turns,
 // in the 4 + 4 form with the 4096-frame window and without the LDS request for a CU of their own: two calls' walk workgroups and an
 // analysis workgroup share a CU (configs[4] shard through the pipeline object: 1.87 - 1.97 -> 1.56 ms per step).
-static inline bool spx_mixed_walk2(const SpxMixedMode& M, bool detached, bool taps, const SpxModeEnv& E) {
-  return M.ahead && !M.concurrent && detached && !taps && !E.walk1;
+static inline bool spx_mixed_walk2(const SpxMixedMode& M, bool detached, bool taps) {
+  return M.ahead && !M.concurrent && detached && !taps;
 }
 
 #endif  // SPX_MODE_H_

@@ -9,9 +9,8 @@
   X(ahead_req) X(overlap_req) X(cu_count) X(lds_per_cu) X(walk_lds) X(walk_waves) X(walk_vgprs) X(walk_fast) X(walk_nwc)        \
   X(lean_lds) X(lean_waves) X(lean_vgprs) X(lean_fast) X(lean_nwc) X(lean_valid) X(tension_lds) X(tension_vgprs)                \
   X(tile_default) X(tile_big) X(tile_small) X(an_lds_default) X(an_lds_small) X(an_vgprs_default) X(an_vgprs_small)             \
-  X(concurrent_enabled) X(chunks_set) X(chunks) X(serial) X(no_lean) X(small_tile) X(ahead_any) X(full_walk) X(walk1)           \
-  X(no_excl) X(trial_force) X(trial_state_key) X(trial_calls) X(trial_choice) X(two_workspaces) X(guard_busy)                   \
-  X(trial_times_ready) X(us_seq) X(us_con) X(trial_key) X(device_ours)
+  X(concurrent_enabled) X(chunks_set) X(chunks) X(trial_state_key) X(trial_calls) X(trial_choice) X(two_workspaces)            \
+  X(guard_busy) X(trial_times_ready) X(us_seq) X(us_con) X(trial_key) X(device_ours)
 #define SPX_A_FIELDS(X)                                                                                                         \
   X(lean_walk) X(launch_lean) X(tile_frames) X(co_resident) X(doubtful) X(trial_slot) X(want_concurrent) X(concurrent)          \
   X(ahead) X(seq_ahead) X(ahead_forced) X(walk2) X(nch) X(exclusive_cu) X(asked_device) X(next_key) X(next_calls) X(next_choice)
@@ -64,9 +63,7 @@ int spx_mode_table_eval(const long long* q, int nq, long long* a, int na) {
   R.tile_default = (int)q[Q_tile_default]; R.tile_big = (int)q[Q_tile_big]; R.tile_small = (int)q[Q_tile_small];
   R.an_lds_default = (size_t)q[Q_an_lds_default]; R.an_lds_small = (size_t)q[Q_an_lds_small];
   R.an_vgprs_default = (int)q[Q_an_vgprs_default]; R.an_vgprs_small = (int)q[Q_an_vgprs_small];
-  E.concurrent_enabled = q[Q_concurrent_enabled]; E.chunks_set = q[Q_chunks_set]; E.chunks = (int)q[Q_chunks]; E.serial = q[Q_serial];
-  E.no_lean = q[Q_no_lean]; E.small_tile = q[Q_small_tile]; E.ahead_any = q[Q_ahead_any]; E.full_walk = q[Q_full_walk];
-  E.walk1 = q[Q_walk1]; E.no_excl = q[Q_no_excl]; E.trial_force = (int)q[Q_trial_force];
+  E.concurrent_enabled = q[Q_concurrent_enabled]; E.chunks_set = q[Q_chunks_set]; E.chunks = (int)q[Q_chunks];
   const SpxModeTrial trial = {q[Q_trial_state_key], (int)q[Q_trial_calls], (int)q[Q_trial_choice]};
   T.two_workspaces = q[Q_two_workspaces]; T.guard_busy = q[Q_guard_busy]; T.trial_times_ready = q[Q_trial_times_ready];
   T.ms_seq = (float)q[Q_us_seq] / 1000.0f; T.ms_con = (float)q[Q_us_con] / 1000.0f; T.trial_key = q[Q_trial_key];
@@ -81,9 +78,10 @@ int spx_mode_table_eval(const long long* q, int nq, long long* a, int na) {
   return 0;
 }
 // a mixed-rate call: groups[g] = {n, walk_lds, walk_waves, walk_vgprs, any_nonlinear, an_lds, an_vgprs}; out = {concurrent, ahead, chain_analyses, asked_device}
-int spx_mode_table_eval_mixed(const long long* groups, int n_groups, int n_total, int cu_count, long long lds_per_cu, long long tension_lds,
-                              int tension_vgprs, int concurrent_enabled, int serial, int env_mixed_mode, int no_order, int ahead_req,
-                              int guard_busy, int device_ours, long long* out4) {
+// (spx_choose_mixed_mode's inputs as they are now; the earlier spx_mode_table_eval_mixed also took the removed A/B switches, and a
+// caller of that signature now finds no symbol instead of passing an integer where out4 is expected)
+int spx_mode_table_mixed_mode(const long long* groups, int n_groups, int n_total, int cu_count, long long lds_per_cu, long long tension_lds,
+                              int tension_vgprs, int concurrent_enabled, int ahead_req, int guard_busy, int device_ours, long long* out4) {
   SpxModeGroup G[8];
   if (n_groups < 0 || n_groups > 8) return -1;
   for (int g = 0; g < n_groups; g++) {
@@ -96,22 +94,19 @@ int spx_mode_table_eval_mixed(const long long* groups, int n_groups, int n_total
   }
   SpxModeEnv E;
   memset(&E, 0, sizeof(E));
-  E.concurrent_enabled = concurrent_enabled; E.serial = serial; E.chunks = 1; E.trial_force = -1;
+  E.concurrent_enabled = concurrent_enabled; E.chunks = 1;
   SpxModeRuntime T;
   memset(&T, 0, sizeof(T));
   long long ours = device_ours;
   T.guard_busy = guard_busy; T.device_ours = ours_cb; T.device_ctx = &ours;
   const SpxMixedMode M = spx_choose_mixed_mode(G, n_groups, n_total, cu_count, (size_t)lds_per_cu, (size_t)tension_lds, tension_vgprs, E,
-                                               env_mixed_mode, no_order != 0, ahead_req != 0, T);
+                                               ahead_req != 0, T);
   out4[0] = M.concurrent; out4[1] = M.ahead; out4[2] = M.chain_analyses; out4[3] = M.asked_device;
   return 0;
 }
 // spx_mixed_walk2 for a decided mixed mode {concurrent, ahead}
-int spx_mode_table_mixed_walk2(int concurrent, int ahead, int detached, int taps, int walk1) {
+int spx_mode_table_mixed_walk2(int concurrent, int ahead, int detached, int taps) {
   SpxMixedMode M = {concurrent != 0, ahead != 0, false, false};
-  SpxModeEnv E;
-  memset(&E, 0, sizeof(E));
-  E.walk1 = walk1 != 0;
-  return spx_mixed_walk2(M, detached != 0, taps != 0, E) ? 1 : 0;
+  return spx_mixed_walk2(M, detached != 0, taps != 0) ? 1 : 0;
 }
 }

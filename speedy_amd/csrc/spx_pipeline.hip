@@ -13,7 +13,7 @@
 // Why the gather kernel writes host memory itself: the produced size is known on the device only.  A device-to-host copy of the
 // exact size needs the host to wait for the batch first (round 4's bench loop did, and the wait kept it from running ahead:
 // 2.3-3.5 ms per batch with the pipelined calls); a copy of the capacity moves three times the bytes.  The kernel needs neither,
-// and it is narrow (SPX_PIPE_PACK_WGS workgroups): PCIe writes are posted, a few waves keep the link busy, and the CUs stay with the
+// and it is narrow (pack_wgs workgroups): PCIe writes are posted, a few waves keep the link busy, and the CUs stay with the
 // chains of the next batches' walk kernels -- the runtime's own copy kernel is launched full-width.
 // Measured against it (round 5, profiles/r05/r5s_copy_out.txt): the gathered frames to HBM first and out by hipMemcpyAsync, sized
 // from the last batch that came back (the rest of a batch that outgrew the copy fetched at wait time) -- the runtime performs
@@ -34,11 +34,7 @@ int spx_internal_run_mixed(const spx_plan_t* plans, int n_plans, const spx_strea
                            void* done_event, bool detached);
 void spx_internal_set_error(const char* msg);
 
-#ifdef SPX_TUNING
-#define SPX_PIPE_MAX_DEPTH 24   // (the developers' build: deeper pipelines for the walk-stream experiments)
-#else
 #define SPX_PIPE_MAX_DEPTH 8
-#endif
 #define PIPE_ALIGN 32   // int16 values: every stream's region starts at a 64-byte boundary, in device and in host memory
 
 // Offsets of the packed output: exclusive prefix sums of the streams' produced values, each rounded up to PIPE_ALIGN; written
@@ -187,13 +183,6 @@ static int pipeline_build(spx_pipeline* p) {
   p->ws_bytes = p->mixed ? spx_batch_workspace_bytes_mixed(p->plans.data(), (int)p->plans.size(), p->jobs.data(), p->plan_index.data(), n)
                          : spx_batch_workspace_bytes(p->plans[0], p->jobs.data(), n);
   if (!p->ws_bytes) return -1;
-#ifdef SPX_TUNING
-  // A/B: where the run stream lands among the hardware queues (dummy streams created in front of it), its priority, the null stream
-  if (const char* e = getenv("SPX_PIPE_DUMMY_STREAMS")) for (int i = 0; i < atoi(e); i++) { hipStream_t d; (void)hipStreamCreateWithFlags(&d, hipStreamNonBlocking); }
-  if (getenv("SPX_PIPE_NULL_STREAM")) p->s_run = nullptr;
-  else if (const char* e = getenv("SPX_PIPE_PRIO")) { PCHK(hipStreamCreateWithPriority(&p->s_run, hipStreamNonBlocking, atoi(e))); }
-  else
-#endif
   PCHK(hipStreamCreateWithFlags(&p->s_run, hipStreamNonBlocking));
   PCHK(hipStreamCreateWithFlags(&p->s_h2d, hipStreamNonBlocking));
   const size_t tab_bytes = (size_t)n * (2 * sizeof(int64_t) + sizeof(int));
@@ -219,9 +208,6 @@ static int pipeline_build(spx_pipeline* p) {
     PCHK(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming));
   }
   PCHK(hipDeviceSynchronize());   // the memsets above ran on the null stream; the pipeline's streams do not wait for it
-#ifdef SPX_TUNING
-  if (const char* e = getenv("SPX_PIPE_PACK_WGS")) p->pack_wgs = atoi(e) > 0 ? atoi(e) : p->pack_wgs;
-#endif
   return 0;
 }
 
@@ -329,10 +315,6 @@ int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_devic
     const int* d_ch = reinterpret_cast<const int*>(p->d_tab + 2 * (size_t)n);
     hipLaunchKernelGGL(spx_pipe_offsets_kernel, dim3(1), dim3(256), 0, p->s_run, S.d_nout, d_ch, d_cap, n, S.d_offsets, S.h_meta, S.h_meta + n + 1);
     const int wgs = n < p->pack_wgs ? n : p->pack_wgs;
-#ifdef SPX_TUNING
-    static const bool no_gather = getenv("SPX_PIPE_NO_GATHER") != nullptr;   // DIAGNOSTIC: what the gather kernel costs the others (no output!)
-    if (!no_gather)
-#endif
     hipLaunchKernelGGL(spx_pipe_copy_kernel, dim3(wgs), dim3(256), 0, p->s_run, S.d_out, d_off, S.d_offsets, n, S.h_out);
   }
   if (!event_recorded) PCHK(hipEventRecord(S.ev_done, p->s_run));

@@ -222,7 +222,6 @@ void spx_plan_destroy(spx_plan_t plan) {
   for (auto& e : plan->trial.ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : plan->ev_walk) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
   for (auto& e : plan->ev_call) if (e) (void)hipEventDestroy(e);
-  for (auto& e : plan->ev_split) if (e) (void)hipEventDestroy(e);
   for (auto& g : plan->stage) {
     if (g.done) { (void)hipEventSynchronize(g.done); (void)hipEventDestroy(g.done); }
     if (g.p) (void)hipHostFree(g.p);

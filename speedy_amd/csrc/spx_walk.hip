@@ -890,33 +890,13 @@ spx_walk_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const in
   }
 }
 
-// Tuning knobs from the environment, read ONCE per process (never on the launch path).
-struct WalkTuning {
-  bool generic, old_fast;
-  int nw, nwm, nwc, wcap;
-};
-static const WalkTuning& walk_tuning() {
-  static const WalkTuning T = [] {
-    WalkTuning t;
-    auto geti = [](const char* k) { const char* e = spx_tuning_env(k); return e ? atoi(e) : -1; };
-    t.generic = spx_tuning_env("SPX_WALK_GENERIC") != nullptr;   // force the general kernel
-    t.old_fast = spx_tuning_env("SPX_WALK_OLD") != nullptr;      // mono speed-up batches on spx_walk_kernel<NW, 1> (A/B only)
-    t.nw = geti("SPX_WALK_NW");
-    t.nwm = geti("SPX_WALK_NWM");
-    t.nwc = geti("SPX_WALK_NWC");
-    t.wcap = geti("SPX_WALK_WCAP");
-    return t;
-  }();
-  return T;
-}
-
 // Which kernel variant a batch gets: 0 general, 1 speed-up mono, 2 speed-up multi-channel.  FAST: all streams speeding
 // up (speed > 1, 0 <= nonlinear <= 1: the stage never sees a speed below 1), decimated search, at most 128 lags in the coarse
 // search (more than 64: the wide-coarse instantiations, round 5 -- 11.025 kHz has 72) and 121 in the refine search (rates below 64 kHz; spx_walk_fast_supports has the last word per wave count), and
 // skip x channels <= 56 (the refill's exact division of the decimated planes).
 static int walk_mode(const SpxPlanDev& P, int maxC, bool speedup_only) {
   if (speedup_only && P.skip >= 2 && (P.maxPeriod / P.skip - P.minPeriod / P.skip + 1) <= 128 && (8 * P.skip + 1) <= 121 &&
-      P.skip * maxC <= 56 && maxC <= 8 && !walk_tuning().generic)
+      P.skip * maxC <= 56 && maxC <= 8)
     return (maxC == 1) ? 1 : 2;
   return 0;
 }
@@ -926,16 +906,13 @@ static int walk_mode(const SpxPlanDev& P, int maxC, bool speedup_only) {
 SpxWalkConfig spx_walk_config(const SpxPlanDev& P, int n_streams, int maxC, bool speedup_only, bool short_jobs, bool lean, bool any_speed,
                               bool short_window) {
   if (maxC < 1) maxC = 1;
-  const WalkTuning& T = walk_tuning();
   SpxWalkConfig c;
-  static const bool no_slow_fast = spx_tuning_env("SPX_NO_SLOW_FAST") != nullptr;   // A/B: slow-down batches on the general kernel
-  const bool slow = !speedup_only && any_speed && !no_slow_fast;
+  const bool slow = !speedup_only && any_speed;
   c.mode = walk_mode(P, maxC, speedup_only || slow);
-  c.fast_kernel = ((c.mode == 1 || c.mode == 2) && !T.old_fast);  // spx_walk_fast_kernel: mono and (round 2) multi-channel
+  c.fast_kernel = c.mode == 1 || c.mode == 2;  // spx_walk_fast_kernel: mono and (round 2) multi-channel
   // Waves per stream of spx_walk_kernel.  Measured on MI355X, 10 s streams (ms per call; 2 / 4 / 8 waves): 256 streams
   // 3.67 / 3.19 / 2.91 (walk kernel alone), 512: 5.40 / 4.78 / 5.63, 1024: 10.3 / 9.3 / 10.5, 2048: 19.7 / 17.7 / -.
   c.nw = (n_streams <= 256) ? 8 : 4;
-  if (T.nw > 0) c.nw = T.nw;
   // spx_walk_fast_kernel: search waves + output waves, window frames.  Three regimes (MI355X, 16 kHz mono x 10 s, ms per call;
   // profiles/r03/r03l_tp_variants.txt):
   //   up to two streams per CU: 4 search + 4 output waves, 4096-frame window -- a stream's chain is the run time, the
@@ -968,25 +945,17 @@ SpxWalkConfig spx_walk_config(const SpxPlanDev& P, int n_streams, int maxC, bool
   // long jobs with at most two streams per CU on the rate-specialised kernels with output waves: the 8192-frame window (half
   // as many refills; spx_walk_fast.hip, SPEC = 1)
   // (not for the instantiations that serve slow-down: those exist in their plan-driven form only)
-  if (!throughput && !short_jobs && c.fast_kernel && c.nwm == 4 && c.nwc == 4 && (P.rate == 16000 || P.rate == 22050) && T.nwm <= 0 &&
-      T.nwc < 0 && !slow) c.wcap = 8192;
+  if (!throughput && !short_jobs && c.fast_kernel && (P.rate == 16000 || P.rate == 22050) && !slow) c.wcap = 8192;
   // rates from 24 kHz (the eight-search-wave form): a step needs up to 2 x maxRequired frames of window, so the 4096-frame window
   // is refilled every ~2 700 frames at 44.1 kHz -- 160 times per 10 s stream; twice the window, a third of the refills
-  if (!throughput && !short_jobs && c.fast_kernel && P.skip >= 6 && T.wcap <= 0) c.wcap = 8192;
+  if (!throughput && !short_jobs && c.fast_kernel && P.skip >= 6) c.wcap = 8192;
   if (lean && !throughput) { c.nwc = 0; c.wcap = 4096; }
   if (short_window && !throughput && P.skip < 6 && c.wcap > 4096) c.wcap = 4096;
-  if (T.nwm > 0) c.nwm = T.nwm;
-  if (T.nwc >= 0) c.nwc = T.nwc;
-  if (T.wcap > 0) c.wcap = T.wcap;
   const int need = P.maxRequired + 2 * P.skip + 2;
   if (c.wcap < 2 * need) c.wcap = 2 * need;
   c.wcap = (c.wcap + 7) & ~7;
-  if (c.nwm != 2 && c.nwm != 4 && c.nwm != 8) c.nwm = 4;
-#ifndef SPX_TUNING
-  c.nwc = c.nwc >= 4 ? 4 : 0;          // the shipped library's forms (spx_walk_fast.hip SPX_FAST_FORMS)
+  c.nwc = c.nwc >= 4 ? 4 : 0;          // the library's forms (spx_walk_fast.hip SPX_FAST_FORMS)
   if (c.nwm == 2) c.nwc = 0;
-#endif
-  if (c.nwm == 8 && P.skip < 6) c.nwm = 4;   // the eight-search-wave form's sum buffers exist in the LDS layout from skip 6 on
   while (c.fast_kernel && !spx_walk_fast_supports(P, c.nwm)) {  // the coarse triangle must fit the search lanes
     if (c.nwm < 4) c.nwm = 4; else if (c.nwm < 8) c.nwm = 8; else c.fast_kernel = false;
   }
@@ -1014,13 +983,8 @@ int spx_walk_kernel_regs(const SpxPlanDev& P, int n_streams, int maxC, bool spee
 #define SPX_FN_W(NWV) (cfg.mode == 1 ? reinterpret_cast<const void*>(spx_walk_kernel<NWV, 1>)   \
                        : cfg.mode == 2 ? reinterpret_cast<const void*>(spx_walk_kernel<NWV, 2>) \
                                        : reinterpret_cast<const void*>(spx_walk_kernel<NWV, 0>))
-  switch (cfg.nw) {
-    case 1: fn = SPX_FN_W(1); break;
-    case 2: fn = SPX_FN_W(2); break;
-    case 8: fn = SPX_FN_W(8); break;
-    case 16: fn = SPX_FN_W(16); break;
-    default: fn = SPX_FN_W(4); break;
-  }
+  if (cfg.nw == 8) fn = SPX_FN_W(8);
+  else fn = SPX_FN_W(4);
 #undef SPX_FN_W
   return spx_kernel_vgprs(fn, scratch_bytes);
 }
@@ -1065,16 +1029,7 @@ void spx_launch_walk(const SpxPlanDev& P, const SpxStreamDev* streams, int n_str
       hipLaunchKernelGGL((spx_walk_kernel<NWV, 0>), dim3(n_streams), dim3(64 * NWV), LY.total, st, P, streams,   \
                          in, out, n_out, states, scratch, maxC, speed_ready);                                    \
   } while (0)
-#ifdef SPX_STAMPS
-  if (nw == 4) SPX_LAUNCH_WALK(4); else SPX_LAUNCH_WALK(8);  // the diagnostic build carries two kernels only
-  return;
-#endif
-  switch (nw) {
-    case 1: SPX_LAUNCH_WALK(1); break;
-    case 2: SPX_LAUNCH_WALK(2); break;
-    case 8: SPX_LAUNCH_WALK(8); break;
-    case 16: SPX_LAUNCH_WALK(16); break;
-    default: SPX_LAUNCH_WALK(4); break;
-  }
+  if (nw == 8) SPX_LAUNCH_WALK(8);
+  else SPX_LAUNCH_WALK(4);
 #undef SPX_LAUNCH_WALK
 }

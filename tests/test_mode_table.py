@@ -33,7 +33,7 @@ def table():
         q.update(dict(zip(res["fields"], res["shapes"][shape])))
         rate, ch, n, sp = (int(v) for v in shape.split(","))
         q.update(n=n, max_channels=ch, do_a=1, do_w=1, has_frames=1, force_total_streams=n, concurrent_enabled=1, chunks=1,
-                 trial_force=-1, trial_state_key=-1, trial_choice=-1, trial_key=77, device_ours=1)
+                 trial_state_key=-1, trial_choice=-1, trial_key=77, device_ours=1)
         q.update(kw)
         qa = (C.c_longlong * len(qf))(*[int(q[f]) for f in qf])
         aa = (C.c_longlong * len(af))()
@@ -150,33 +150,36 @@ def test_separate_halves_guard_and_forced_groups(table):
     assert (kind(a), a["exclusive_cu"]) == ("sequence", 0)
 
 
-def test_mixed_rate_call(table):
+def test_mixed_rate_decision(table):
     """spx_choose_mixed_mode on BASELINE configs[4]'s shard: 128 streams at 16 kHz, 128 at 22.05 kHz, half of each stereo."""
     L = table.lib
     r16 = dict(zip(table.res["fields"], table.res["shapes"]["16000,2,128,1"]))
     r22 = dict(zip(table.res["fields"], table.res["shapes"]["22050,2,128,1"]))
-    groups = []
-    for r in (r16, r22):
-        groups += [128, r["walk_lds"], r["walk_waves"], r["walk_vgprs"], 1, r["an_lds_default"], r["an_vgprs_default"]]
-    g = (C.c_longlong * len(groups))(*groups)
     out = (C.c_longlong * 4)()
 
-    def mixed(n_total=256, enabled=1, serial=0, ahead=0, busy=0, ours=1, env_mixed=-1):
-        assert L.spx_mode_table_eval_mixed(g, 2, n_total, r16["cu_count"], r16["lds_per_cu"], r16["tension_lds"], r16["tension_vgprs"],
-                                           enabled, serial, env_mixed, 0, ahead, busy, ours, out) == 0
+    def mixed(rows=(r16, r22), streams=128, n_total=256, enabled=1, ahead=0, busy=0, ours=1):
+        groups = []
+        for r in rows:
+            groups += [streams, r["walk_lds"], r["walk_waves"], r["walk_vgprs"], 1, r["an_lds_default"], r["an_vgprs_default"]]
+        g = (C.c_longlong * len(groups))(*groups)
+        assert L.spx_mode_table_mixed_mode(g, len(rows), n_total, r16["cu_count"], r16["lds_per_cu"], r16["tension_lds"],
+                                           r16["tension_vgprs"], enabled, ahead, busy, ours, out) == 0
         return dict(concurrent=out[0], ahead=out[1], chain=out[2], asked=out[3])
     assert mixed() == dict(concurrent=0, ahead=0, chain=1, asked=0)          # 2 x 128 + 48 + 2 x 168 > 512: kernels in sequence, analyses chained
     assert mixed(ahead=1) == dict(concurrent=0, ahead=1, chain=1, asked=1)   # spx_batch_run_mixed_ahead
     assert mixed(ahead=1, ours=0)["ahead"] == 0 and mixed(ahead=1, enabled=0)["ahead"] == 0
     assert mixed(n_total=2048, ahead=1)["ahead"] == 0
-    # a mix that WOULD run concurrently (here: said so by the tuning switch) and finds another concurrent call in flight runs in
-    # sequence -- and, asked to, still pipelined with its predecessor (round 5 computed `ahead` before the busy guard: ADVICE r5)
-    assert mixed(env_mixed=1)["concurrent"] == 1
-    assert mixed(env_mixed=1, busy=1) == dict(concurrent=0, ahead=0, chain=1, asked=1)
-    assert mixed(env_mixed=1, busy=1, ahead=1) == dict(concurrent=0, ahead=1, chain=1, asked=1)
+    # a mix that runs concurrently -- two 16 kHz mono groups of 64 streams: 9 457 664 / 126 065 + 1 536 / 29 = 75 + 52 < 256 CUs
+    # closed, 73 888 + 2 x 37 776 bytes of LDS, 2 x 96 + 48 + 2 x 128 = 496 registers -- and finds another concurrent call in flight
+    # runs in sequence -- and, asked to, is still pipelined with its predecessor (round 5 computed `ahead` before the busy guard: ADVICE r5)
+    r16m = dict(zip(table.res["fields"], table.res["shapes"]["16000,1,64,1"]))
+    pair = dict(rows=(r16m, r16m), streams=64, n_total=128)
+    assert mixed(**pair)["concurrent"] == 1
+    assert mixed(**pair, busy=1) == dict(concurrent=0, ahead=0, chain=1, asked=1)
+    assert mixed(**pair, busy=1, ahead=1) == dict(concurrent=0, ahead=1, chain=1, asked=1)
     # round 6: the walk kernels of consecutive mixed calls overlap only for a pipelined, detached call without taps
-    # (spx_mixed_walk2: concurrent, ahead, detached, taps, the walk1 switch)
+    # (spx_mixed_walk2: concurrent, ahead, detached, taps)
     w2 = L.spx_mode_table_mixed_walk2
-    assert w2(0, 1, 1, 0, 0) == 1
-    assert w2(0, 1, 0, 0, 0) == 0 and w2(0, 0, 1, 0, 0) == 0 and w2(1, 0, 1, 0, 0) == 0
-    assert w2(0, 1, 1, 1, 0) == 0 and w2(0, 1, 1, 0, 1) == 0
+    assert w2(0, 1, 1, 0) == 1
+    assert w2(0, 1, 0, 0) == 0 and w2(0, 0, 1, 0) == 0 and w2(1, 0, 1, 0) == 0
+    assert w2(0, 1, 1, 1) == 0

@@ -1,6 +1,5 @@
 #!/bin/bash
-# GPU box: A/B of library builds / tuning variables on the bench workload, interleaved so that drift cancels.
-# (tuning variables need the tuning build: make -C speedy_amd/csrc tuning; SPEEDY_HIP_LIB=$PWD/speedy_amd/lib/ab/libspeedy_hip_tuning.so)
+# GPU box: A/B of library builds / environment variables on the bench workload, interleaved so that drift cancels.
 #   bash tools/ab_lib.sh TAG REPS "label|ENV=.. ENV=.." "label2|..." ...
 # e.g. bash tools/ab_lib.sh r02x 2 "new|" "base|SPEEDY_HIP_LIB=$PWD/speedy_amd/lib/ab/libspeedy_hip_base.so"
 TAG=${1:-ab}; REPS=${2:-2}; shift; shift
