@@ -16,7 +16,8 @@
  * streams with staged work run as one launch sequence when a result is first asked for (see
  * speedyHipSetCoalescing below; streams with callbacks, a rate stage or mode switches run their own
  * sequence per write).  The sequence of output samples, and the count available after each write,
- * equal the reference's.
+ * equal the reference's -- except with the opt-in ready reads (SPEEDY_HIP_COALESCE_READY below), where
+ * the samples are the same and only the count per read differs.
  */
 #ifndef SPEEDY_HIP_SONIC2_H_
 #define SPEEDY_HIP_SONIC2_H_
@@ -94,12 +95,38 @@ sonicStream speedyHipCreateSonicStream(int sampleRate, int numChannels, int matc
  * first call that needs a result on such a stream (a read, sonicSamplesAvailable, a setter ...) runs everything that is
  * staged on ANY stream of the device in one launch sequence.  Per-stream results are those of the reference call for
  * call; a server that writes to all its streams and then reads from all of them pays one launch sequence per round
- * instead of one per stream.  Streams of one device may be used from different threads (the pool is locked). */
+ * instead of one per stream.  Streams of one device may be used from different threads (the pool is locked).
+ * speedyHipSetCoalescing(SPEEDY_HIP_COALESCE_READY), or SPX_POOL_READY=1 in the environment (SPX_NO_POOL wins when both
+ * are set), makes new streams coalesced with READY READS, below; speedyHipGetCoalescing() then returns 2. */
 void speedyHipSetCoalescing(int on);
 int speedyHipGetCoalescing(void);
+/* Coalesced with ready reads: a read returns what is already on the host and never waits for the GPU (opt-in).  For such
+ * a stream (created with coalesce = SPEEDY_HIP_COALESCE_READY below, or under that process-wide default):
+ *  1. sonicWriteShortToStream / sonicWriteFloatToStream / sonicFlushStream only stage, as for every coalesced stream, and
+ *     do not wait -- not even while the stream's previous work is still running on the GPU.  Exceptions: bounded staging
+ *     (SPX_POOL_STAGE_BYTES, default 8 MiB, or 8 192 staged writes pool-wide) may run what is staged and wait for it, and a
+ *     write behind a flush that is still staged waits for that flush to run.
+ *  2. sonicReadShortFromStream / sonicReadFloatFromStream / sonicSamplesAvailable never wait for GPU work (but see 3).
+ *     Each call (a) completes the device's run in flight if the GPU has finished it (a query, not a wait): its frames
+ *     reach their streams' host copies; (b) if no run is in flight and anything is staged on any stream, launches the
+ *     next run and does not wait for it; (c) returns up to bufferSize of the frames this stream holds on the host (0 is
+ *     a legal answer: "nothing ready").  The read that launches a stream's work therefore never returns that work's frames.
+ *  3. After sonicFlushStream the next read (or sonicSamplesAvailable) waits until everything staged on the stream up to
+ *     and including the flush has been delivered; reads then return frames until none are left, then 0.  The drain loop
+ *     `do n = sonicReadShortFromStream(...); while (n > 0);` behind a flush collects all the audio.  A write after the
+ *     drain starts a new staging phase, non-blocking again.
+ *  4. The audio is unchanged: the sequence of frames a stream delivers over its life is bit for bit what the default mode
+ *     (and the reference) deliver for the same writes, setters and flush.  Only the count per read differs; the frames
+ *     delivered so far never exceed the reference's readable count at that point.
+ *  5. Everything else may wait as before: setters, a second flush, sonicDestroyStream, sonicIntGetSpeed and leaving the
+ *     coalesced path (a monitoring callback, sonicSetRate != 1, a switch between linear and nonlinear, sonicInt* calls)
+ *     first complete any run the stream is part of.  A stream that leaves the coalesced path reads the blocking way again:
+ *     ready reads exist only where coalescing does. */
+#define SPEEDY_HIP_COALESCE_READY 2
 /* sonicCreateStream with the hysteresis shape AND the execution path chosen for this handle alone: coalesce = -1 the
- * process-wide default above, 0 = the handle runs its own launch sequence per write, 1 = coalesced.  Nothing process-wide
- * is read or written for an explicit 0 / 1, so handles of both kinds can be created from several threads at once. */
+ * process-wide default above, 0 = the handle runs its own launch sequence per write, 1 = coalesced, 2 =
+ * SPEEDY_HIP_COALESCE_READY (coalesced with ready reads).  Nothing process-wide is read or written for an explicit 0 / 1 / 2,
+ * so handles of all kinds can be created from several threads at once. */
 sonicStream speedyHipCreateSonicStreamEx(int sampleRate, int numChannels, int matchMatlab, int coalesce);
 /* Launch sequences run / stream jobs served by the current device's pool so far. */
 void speedyHipPoolStats(unsigned long long* runs, unsigned long long* jobs);

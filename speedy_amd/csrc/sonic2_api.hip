@@ -23,7 +23,8 @@
 // handle with monitoring callbacks, a rate stage, sonicInt* calls or a mode switch needs.  COALESCED (sonic2_pool.hip):
 // every other handle; writes and flushes are only staged, and the first call that needs results on any waiting handle
 // runs ONE launch sequence for all of them (the kernels take N-stream job tables).  Same kernels, same jobs
-// (spx_prepare_job / spx_finish_job serve both), same results call for call.
+// (spx_prepare_job / spx_finish_job serve both), same results call for call -- or, for a coalesced handle with ready reads
+// (SPEEDY_HIP_COALESCE_READY), the same frames with reads that hand out only what is already on the host.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -84,9 +85,9 @@ sonicStream sonicCreateStream(int sampleRate, int numChannels) {
 sonicStream speedyHipCreateSonicStream(int sampleRate, int numChannels, int matchMatlab) {
   return speedyHipCreateSonicStreamEx(sampleRate, numChannels, matchMatlab, -1);
 }
-// coalesce: -1 = the process-wide default (speedyHipSetCoalescing / SPX_NO_POOL), 0 = this handle runs its own launch
-// sequence per write, 1 = this handle is coalesced whatever the default says.  The choice is the handle's: nothing
-// process-wide is written here.
+// coalesce: -1 = the process-wide default (speedyHipSetCoalescing / SPX_NO_POOL / SPX_POOL_READY), 0 = this handle runs its
+// own launch sequence per write, 1 = this handle is coalesced whatever the default says, 2 = coalesced with ready reads
+// (SPEEDY_HIP_COALESCE_READY).  The choice is the handle's: nothing process-wide is written here.
 sonicStream speedyHipCreateSonicStreamEx(int sampleRate, int numChannels, int matchMatlab, int coalesce) {
   if (numChannels < 1) { g_api_err = "sonicCreateStream: numChannels < 1"; return nullptr; }
   int ndev = 0;
@@ -121,14 +122,16 @@ sonicStream speedyHipCreateSonicStreamEx(int sampleRate, int numChannels, int ma
   s->dState = reinterpret_cast<SpxStreamState*>(s->dSmall + 256);
   s->dNOut = reinterpret_cast<int64_t*>(s->dSmall + 256 + sizeof(SpxStreamState));  // directly behind the state
   s->dRate = reinterpret_cast<SpxRateState*>(s->dSmall + 256 + sizeof(SpxStreamState) + sizeof(int64_t));
-  if (SpxPool* pool = spx_pool_for_device(s->device, coalesce)) spx_pool_adopt(pool, s);
+  const int mode = spx_pool_mode(coalesce);
+  if (SpxPool* pool = mode ? spx_pool_for_device(s->device, mode) : nullptr) spx_pool_adopt(pool, s, mode == SPEEDY_HIP_COALESCE_READY);
   return s;
 }
 
 void sonicDestroyStream(sonicStream s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  if (s->pooled) spx_pool_forget(s);   // off the waiting list; its buffers were only ever used on the pool's (idle) stream
+  if (s->pooled) spx_pool_forget(s);   // off the waiting list; its buffers were only ever used on the pool's stream, which
+                                       // forget leaves idle (it completes a run in flight first, a ready read's detached one too)
   if (s->hs) (void)hipStreamSynchronize(s->hs);
   s->dIn.release(s->hs); s->dTsm.release(s->hs); s->dOut.release(s->hs); s->dFinal.release(s->hs); s->dRec.release(s->hs); s->dScr.release(s->hs);
   s->tTension.release(s->hs); s->tSpeed.release(s->hs); s->tFeatures.release(s->hs); s->tSpec.release(s->hs);
@@ -290,7 +293,7 @@ int spx_prepare_job(sonicStream s, bool flush, bool direct, hipStream_t hs, SpxP
   const int64_t fa = s->framesDone;
   const bool taps = nonlinear && any_callback(s);
   J.hasRing = hasRing; J.nonlinear = nonlinear; J.taps = taps; J.flush = flush; J.direct = direct;
-  J.T = T; J.fa = fa;
+  J.T = T; J.fa = fa; J.nIn = s->nIn;
 
   // ---- ring buffers this job hands to the TSM stage (the kernel counts the same way: spx_walk.hip events) ----
   const int64_t handedBefore = s->handedHost;
@@ -429,7 +432,7 @@ void spx_finish_job(sonicStream s, const SpxJobPlan& J) {
     // moves to its write index -- tension frames below it that were not computed yet never will be; sonicIntFlushStream
     // then pads 2*maxRequired zeros, which later input follows in TSM coordinates
     if (J.hasRing && !J.direct) {
-      s->tensionSkip = std::max(s->tensionSkip, s->nIn / P.B);
+      s->tensionSkip = std::max(s->tensionSkip, J.nIn / P.B);
       s->tensionDone = std::max(s->tensionDone, s->tensionSkip);
     }
     s->tsmShift += 2 * (int64_t)P.maxRequired;
@@ -623,6 +626,7 @@ float sonicIntGetSpeed(sonicStream s) {
 }
 
 int sonicSamplesAvailable(sonicStream s) {
+  if (s->pooled && s->readyReads) return spx_pool_available(s);
   if (!sync_stream(s)) return 0;
   return (int)((s->rateMode ? s->finKnown : s->outKnown) - s->outRead);
 }

@@ -33,6 +33,17 @@
 //   * a call on a handle that is part of the run in flight waits for that run (its state is the run's until the results are in).
 // Results per handle are what they always were: the jobs are formed per handle from that handle's own staged writes.
 //
+// Ready reads (SPEEDY_HIP_COALESCE_READY, opt-in per handle or process-wide; sonic2.h states the contract).  With the reference's
+// call order a blocking read keeps one write per thread outstanding, so a launch sequence carries one handle per thread.  A read of
+// a ready-reads handle instead (a) completes the run in flight if a stream query says it is done, (b) launches everything staged
+// if no run is in flight -- "detached": it returns without waiting -- and (c) hands out what the handle's host copy holds.  A run
+// is split in two halves for that: launch_run (up to the gather launch) and complete_run (the host side of the results), which
+// any thread may run once the stream is done; whoever needs a detached run over first (a blocking read, a setter, a destroy, a
+// handle leaving the pool) takes it over in wait_for_run.  Meanwhile the run's ready handles go on staging into the other input
+// area; their later writes stay on their own lists for the next run, and completion takes what the job consumed from the job
+// (SpxJobPlan::nIn), not from the handle.  Still one run in flight per pool.  After a flush the handle's next read waits for
+// everything up to the flush, so the reference's drain loop collects all of it.
+//
 // Device memory: a handle keeps its own sliding input / output allocations (sonic2_stream.h); the kernels of a pooled
 // launch get NULL base pointers and per-stream offsets that are the allocations' absolute element addresses.  The
 // per-frame arrays (records, scratch) are indexed by the kernels through ONE offset per stream, so for pooled handles
@@ -50,7 +61,7 @@
 
 #include "sonic2_stream.h"
 
-static std::atomic<int> g_coalesce{-1};   // -1: not decided yet (environment), 0 off, 1 on
+static std::atomic<int> g_coalesce{-1};   // -1: not decided yet (environment), 0 off, 1 on, 2 on with ready reads
 
 struct PinBuf {   // growable pinned host area
   unsigned char* p = nullptr;
@@ -88,8 +99,10 @@ struct PoolResult { SpxStreamState st; int64_t n; };
 
 struct SpxPool {
   std::mutex mu;
-  std::condition_variable cv;      // a run has finished (running -> false, its handles' inRun -> false)
+  std::condition_variable cv;      // a run has finished (running -> false, its handles' inRun -> false), or has become detached
   bool running = false;            // a run owns hTab / hRes / dWs / the stream, and the input area it was staged in
+  std::atomic<bool> detached{false};   // the run in flight was launched by a ready read and nobody waits on it: the first thread
+                                       // that needs it over completes it (wait_for_run); a ready read completes it once it is done
   int waiters = 0;                 // threads inside wait_for_run (mutex)
   std::atomic<unsigned> gen{0};    // runs finished: a waiting thread polls it for a while before it blocks (wait_for_run)
   std::thread::id first_thread;    // the batching look costs a single-threaded caller nothing: only once a second thread is seen
@@ -114,6 +127,10 @@ struct SpxPool {
   size_t dWsCap = 0;
   unsigned long long runs = 0, jobs = 0;   // statistics (speedyHipPoolStats)
   SpxDeferred* defer = nullptr;            // the run in preparation
+  SpxDeferred runDefer;                    // the run's replaced allocations: back to the cache when it is over (end_run)
+  hipError_t launchErr = hipSuccess;       // what the run's launches reported
+  size_t resOut = 0;                       // byte offset of the output slices in hRes
+  std::chrono::steady_clock::time_point tLaunched;
   struct Item { sonicStream s; SpxJobPlan J; std::vector<sonicStreamStruct::Seg> segs; bool flush; };
   std::vector<Item> items;                 // the run's tables (capacity kept from run to run)
   std::vector<PoolCopy> copies;
@@ -130,16 +147,20 @@ static std::mutex g_pools_mu;
 static int coalesce_default() {
   int on = g_coalesce.load();
   if (on < 0) {
-    on = getenv("SPX_NO_POOL") ? 0 : 1;
+    const char* ready = getenv("SPX_POOL_READY");
+    on = getenv("SPX_NO_POOL") ? 0 : (ready && *ready && strcmp(ready, "0") != 0) ? SPEEDY_HIP_COALESCE_READY : 1;
     int expected = -1;
     g_coalesce.compare_exchange_strong(expected, on);   // (a speedyHipSetCoalescing call that raced us wins)
     on = g_coalesce.load();
   }
   return on;
 }
+int spx_pool_mode(int coalesce) {
+  if (coalesce < 0) return coalesce_default();
+  return coalesce == SPEEDY_HIP_COALESCE_READY ? SPEEDY_HIP_COALESCE_READY : (coalesce ? 1 : 0);
+}
 SpxPool* spx_pool_for_device(int device, int coalesce) {
-  const int on = coalesce < 0 ? coalesce_default() : (coalesce ? 1 : 0);
-  if (!on || device < 0 || device >= 64) return nullptr;
+  if (!spx_pool_mode(coalesce) || device < 0 || device >= 64) return nullptr;
   std::lock_guard<std::mutex> g(g_pools_mu);
   if (!g_pools[device]) {
     SpxPool* p = new SpxPool();
@@ -151,9 +172,10 @@ SpxPool* spx_pool_for_device(int device, int coalesce) {
 }
 static SpxPool* pool_of(sonicStream s) { return g_pools[s->device]; }
 
-void spx_pool_adopt(SpxPool* pool, sonicStream s) {
+void spx_pool_adopt(SpxPool* pool, sonicStream s, bool ready) {
   (void)pool;
   s->pooled = true;
+  s->readyReads = ready;
 }
 const SpxFrameRec* spx_pool_arena_rec(SpxPool* pool) { return pool->aRec; }
 
@@ -361,20 +383,34 @@ static bool place_input(SpxPool* P, sonicStream s, const std::vector<sonicStream
   return true;
 }
 
-// A run is over (or could not be launched): its handles belong to their callers again.  Pool mutex held.
+// A run is over (or could not be launched): its handles belong to their callers again, the allocations it replaced return to
+// the block cache (behind everything it enqueued) and its replaced arena ranges to the free lists.  Pool mutex held.
 static void end_run(SpxPool* P, std::vector<sonicStream>& run) {
   for (sonicStream s : run) s->inRun = false;
   run.clear();
+  for (auto& q : P->runDefer.frees) block_free_locked(P, q.first, q.second);
+  P->runDefer.frees.clear();
+  for (auto& r : P->arenaLater) arena_free(P, r.first, r.second);
+  P->arenaLater.clear();
   P->running = false;
+  P->detached.store(false, std::memory_order_release);
   P->gen.fetch_add(1, std::memory_order_release);
   P->cv.notify_all();
 }
 
-// Everything that waits, one launch sequence per (plan, kernel variant) group, one synchronisation.  Called with the pool mutex
-// held through `lk`, with no run in flight; returns with it held.  The mutex is released twice on the way: for the bounded look
-// for more staged work (several threads only), and while the GPU works.
-static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
-  if (P->waiting.empty()) return true;
+static double sec(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+  return std::chrono::duration<double>(b - a).count();
+}
+
+enum RunLaunch { RUN_NONE, RUN_LAUNCHED, RUN_FAILED };
+
+// The launch half of a run: everything that waits, one launch sequence per (plan, kernel variant) group, up to and including the
+// gather launch.  Called with the pool mutex held through `lk`, with no run in flight; returns with it held.  The mutex is released
+// on the way for the bounded look for more staged work (several threads only).  RUN_LAUNCHED: the run is in flight (`running`, its
+// handles `inRun`) and complete_run finishes it once the stream is done; otherwise the run is already over (RUN_NONE: nothing
+// waited or no job was left; RUN_FAILED: the waiting handles could not be served and have failed).
+static RunLaunch launch_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
+  if (P->waiting.empty()) return RUN_NONE;
   P->running = true;   // from here on other threads stage and wait; nobody else starts a run
   if (P->multi) {
     // The combiner's look: threads whose handles the previous run served are writing again right now -- a few microseconds at a
@@ -407,8 +443,11 @@ static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
   P->hCur ^= 1;
   P->hInUsed = 0;
   items.reserve(run.size());
-  SpxDeferred defer;
+  // whatever happens below, the replaced allocations are released by end_run, behind everything enqueued by then
+  SpxDeferred& defer = P->runDefer;
   defer.pool = P;
+  defer.moves.clear();
+  defer.frees.clear();
   P->defer = &defer;
   const auto tp0 = std::chrono::steady_clock::now();
   for (sonicStream s : run) {
@@ -418,7 +457,7 @@ static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
     Item& it = items.back();   // prepared in place
     it.s = s;
     it.segs.clear();
-    it.segs.swap(s->segs);
+    it.segs.swap(s->segs);   // (writes a ready-reads handle stages while the run is in flight start a new list: the next run's)
     it.flush = s->pendingFlush;
     s->pendingFlush = false;
     if (s->failed || !place_input(P, s, it.segs, copies, &defer) || !spx_prepare_job(s, it.flush, false, P->hs, P, it.J, &defer)) {
@@ -427,18 +466,8 @@ static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
     }
   }
   P->defer = nullptr;
-  // whatever happens below, the replaced allocations are released behind everything enqueued so far and the replaced
-  // arena ranges return to the free lists
-  struct Releaser {
-    SpxPool* P; SpxDeferred* d;
-    ~Releaser() {
-      for (auto& q : d->frees) block_free_locked(P, q.first, q.second);
-      for (auto& r : P->arenaLater) arena_free(P, r.first, r.second);
-      P->arenaLater.clear();
-    }
-  } releaser{P, &defer};
   const size_t n = items.size();
-  if (n == 0) { end_run(P, run); return true; }
+  if (n == 0) { end_run(P, run); return RUN_NONE; }
   // moves in pieces of 64 KB, one workgroup each
   std::vector<SpxMove>& moves = P->moves;
   moves.clear();
@@ -476,7 +505,7 @@ static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
   auto give_up = [&](const char* why) {   // nothing was launched: the waiting handles cannot be served
     for (auto& it : items) spx_stream_fail(it.s, why);
     end_run(P, run);
-    return false;
+    return RUN_FAILED;
   };
   if (!P->hTab.reserve(b_tab + 64, 0)) return give_up("pinned table allocation failed");
   size_t res_elems = 0;
@@ -499,7 +528,7 @@ static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
   const size_t w_states = (2 * b_jobs + 63) & ~(size_t)63, w_nout = w_states + ((sizeof(SpxStreamState) * n + 63) & ~(size_t)63);
   const size_t w_total = w_nout + sizeof(int64_t) * n;
   if (w_total > P->dWsCap) {
-    if (P->dWs) (void)hipFree(P->dWs);   // (nothing of this pool is in flight between runs)
+    if (P->dWs) (void)hipFree(P->dWs);   // (this is the run's launch: nothing of the pool is in flight)
     P->dWs = nullptr;
     size_t cap = P->dWsCap ? P->dWsCap : 65536;
     while (cap < w_total) cap *= 2;
@@ -561,31 +590,32 @@ static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
   const unsigned gy = (unsigned)std::min<int64_t>(64, std::max<int64_t>(1, (max_slice + 8191) / 8192));
   hipLaunchKernelGGL(spx_pool_gather_kernel, dim3((unsigned)n, gy), dim3(256), 0, P->hs, hD, dStates, dNout, hR, hOut);
   lap(4);
-  const hipError_t le = hipGetLastError();
-  const auto tp3 = std::chrono::steady_clock::now();
-  // The run is a few tens of microseconds of GPU work: waiting for it in the runtime's blocking way costs about as much
-  // again in wake-up latency.  Poll the stream for a while (SPX_POOL_SPIN_US, default 2000 us), then block.
-  static const long spin_us = [] { const char* e = getenv("SPX_POOL_SPIN_US"); return e ? atol(e) : 2000L; }();
-  // (the mutex is free while the GPU works: other threads stage their next writes -- on handles that are not part of this run --
-  // and queue up behind it; everything this run owns stays untouched until the lock is back)
-  lk.unlock();
-  hipError_t se = hipErrorNotReady;
-  if (spin_us > 0) {
-    const auto t_spin = std::chrono::steady_clock::now();
-    while ((se = hipStreamQuery(P->hs)) == hipErrorNotReady) {
-      if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_spin).count() > (double)spin_us) break;
-    }
-    if (se == hipErrorNotReady) (void)hipGetLastError();
-  }
-  if (se == hipErrorNotReady) se = hipStreamSynchronize(P->hs);
-  lk.lock();
+  P->launchErr = hipGetLastError();
+  P->resOut = o_out;
+  P->tLaunched = std::chrono::steady_clock::now();
+  P->t_prep += sec(tp0, tp1); P->t_tab += sec(tp1, tp2); P->t_launch += sec(tp2, P->tLaunched);
+  return RUN_LAUNCHED;
+}
+
+// The completion half: the run's stream has finished (se: what the query or the synchronisation said).  The jobs' host mirrors,
+// the frames into the handles' host copies, the counters; then the run is over.  Any thread may run it, once per run, pool mutex
+// held.  The values a job consumed come from the job (J.nIn), not from the handle: a ready-reads handle may have staged more since.
+static bool complete_run(SpxPool* P, hipError_t se) {
   const auto tp4 = std::chrono::steady_clock::now();
+  std::vector<SpxPool::Item>& items = P->items;
+  std::vector<sonicStream>& run = P->run;
+  const hipError_t le = P->launchErr;
   if (le != hipSuccess || se != hipSuccess) {
     const std::string why = std::string("coalesced launch failed: ") + hipGetErrorString(le != hipSuccess ? le : se);
     for (auto& it : items) spx_stream_fail(it.s, why);
     end_run(P, run);
     return false;
   }
+  const size_t n = items.size();
+  const std::vector<int64_t>& res_off = P->res_off;
+  const std::vector<int64_t>& res_cap = P->res_cap;
+  const PoolResult* hR = reinterpret_cast<const PoolResult*>(P->hRes.p);
+  const int16_t* hOut = reinterpret_cast<const int16_t*>(P->hRes.p + P->resOut);
   for (size_t i = 0; i < n; i++) {
     sonicStream s = items[i].s;
     spx_finish_job(s, items[i].J);
@@ -614,23 +644,54 @@ static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
     s->curSpeedKnown = hR[i].st.curSpeed;
     s->dirty = false;
     s->writesSinceSync = 0;
-    s->devIn = s->nIn;
+    s->devIn = items[i].J.nIn;
   }
   P->runs++;
   P->jobs += n;
   end_run(P, run);
   const auto tp5 = std::chrono::steady_clock::now();
-  auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-  P->t_prep += sec(tp0, tp1); P->t_tab += sec(tp1, tp2); P->t_launch += sec(tp2, tp3); P->t_wait += sec(tp3, tp4); P->t_post += sec(tp4, tp5);
+  P->t_wait += sec(P->tLaunched, tp4); P->t_post += sec(tp4, tp5);
   return true;
+}
+
+// Wait for the run in flight and complete it: this thread owns the run (it launched it, or found it detached).  The run is a few
+// tens of microseconds of GPU work: waiting for it in the runtime's blocking way costs about as much again in wake-up latency.
+// Poll the stream for a while (SPX_POOL_SPIN_US, default 2000 us), then block.  Pool mutex held through `lk`, released meanwhile
+// (other threads stage their next writes and queue up behind the run; everything the run owns stays untouched until the lock is
+// back).
+static bool await_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
+  P->detached.store(false, std::memory_order_release);   // (from here on other threads wait for `gen`, as for any run)
+  static const long spin_us = [] { const char* e = getenv("SPX_POOL_SPIN_US"); return e ? atol(e) : 2000L; }();
+  lk.unlock();
+  hipError_t se = hipErrorNotReady;
+  if (spin_us > 0) {
+    const auto t_spin = std::chrono::steady_clock::now();
+    while ((se = hipStreamQuery(P->hs)) == hipErrorNotReady) {
+      if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_spin).count() > (double)spin_us) break;
+    }
+    if (se == hipErrorNotReady) (void)hipGetLastError();
+  }
+  if (se == hipErrorNotReady) se = hipStreamSynchronize(P->hs);
+  lk.lock();
+  return complete_run(P, se);
+}
+
+// A blocking run: launch, wait, complete, all in this call.  Pool mutex held, no run in flight.
+static bool pool_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
+  const RunLaunch r = launch_run(P, lk);
+  if (r != RUN_LAUNCHED) return r == RUN_NONE;
+  return await_run(P, lk);
 }
 
 static void enlist(SpxPool* P, sonicStream s) {
   if (!s->poolPending) { s->poolPending = true; P->waiting.push_back(s); }
 }
-// Wait for the run in flight to end.  A run is tens of microseconds: blocking in the kernel costs a thread about as much again to
+// Wait for the run in flight to end.  A run that nobody waits on (detached: a ready read launched it) is completed right here --
+// this thread takes it over.  Otherwise: a run is tens of microseconds, blocking in the kernel costs a thread about as much again to
 // wake up, so it polls the run counter for a while first (mutex released; SPX_POOL_SPIN_US bounds it, 200 us at most), then blocks.
+// The caller loops on its own condition: a run that becomes detached meanwhile ends the wait too, and the next round takes it over.
 static void wait_for_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
+  if (P->detached.load(std::memory_order_acquire)) { (void)await_run(P, lk); return; }
   static const double spin_us = [] { const char* e = getenv("SPX_POOL_SPIN_US"); const double v = e ? atof(e) : 2000.0; return v < 200.0 ? v : 200.0; }();
   const unsigned g0 = P->gen.load(std::memory_order_acquire);
   P->waiters++;
@@ -640,7 +701,7 @@ static void wait_for_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
     lk.unlock();
     const auto t0 = std::chrono::steady_clock::now();
     for (;;) {
-      if (P->gen.load(std::memory_order_acquire) != g0) break;
+      if (P->gen.load(std::memory_order_acquire) != g0 || P->detached.load(std::memory_order_acquire)) break;
       const double waited = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
       if (waited >= spin_us) break;
       // (more waiting threads than CPUs -- a cgroup quota does not show in the affinity mask: after a short pure spin the poll gives
@@ -652,17 +713,22 @@ static void wait_for_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
     }
     lk.lock();
   }
-  if (P->gen.load(std::memory_order_acquire) == g0 && P->running) P->cv.wait(lk);
+  if (P->gen.load(std::memory_order_acquire) == g0 && P->running && !P->detached.load(std::memory_order_acquire)) P->cv.wait(lk);
   P->waiters--;
 }
-// every entry point: which threads use the pool (the batching look is for several), and a handle that is part of the run in
-// flight is the run's until its results are in
-static void enter(SpxPool* P, sonicStream s, std::unique_lock<std::mutex>& lk) {
+// every entry point: which threads use the pool (the batching look is for several)
+static void note_thread(SpxPool* P) {
   if (!P->multi) {
     const std::thread::id me = std::this_thread::get_id();
     if (!P->have_first) { P->first_thread = me; P->have_first = true; }
     else if (P->first_thread != me) P->multi = true;
   }
+}
+// ... and a handle that is part of the run in flight is the run's until its results are in -- except for what only stages (a write
+// or a flush of a ready-reads handle: the staged work goes to the next run, the run in flight does not look at it)
+static void enter(SpxPool* P, sonicStream s, std::unique_lock<std::mutex>& lk, bool stage_only = false) {
+  note_thread(P);
+  if (stage_only && s->readyReads) return;
   while (s->inRun) wait_for_run(P, lk);
 }
 // run what waits until `s` has nothing staged any more (another thread's run may serve it; several runs may pass first)
@@ -679,11 +745,38 @@ static bool run_all_locked(SpxPool* P, std::unique_lock<std::mutex>& lk) {
   while (P->running) wait_for_run(P, lk);
   return pool_run(P, lk);
 }
+// What a read or sonicSamplesAvailable of a ready-reads handle does before it looks at the frames the host holds (sonic2.h,
+// SPEEDY_HIP_COALESCE_READY): (a) a detached run the GPU has finished is completed -- a query, never a wait; (b) with no run in
+// flight, everything staged on any handle is launched, detached, and not waited for.  The read that launches a handle's work
+// therefore never returns that work's frames.  After a flush the read waits instead, until everything up to the flush is in.
+static void ready_step(SpxPool* P, sonicStream s, std::unique_lock<std::mutex>& lk) {
+  note_thread(P);
+  if (s->flushWait) {
+    (void)settle_locked(P, s, lk);
+    s->flushWait = false;
+    return;
+  }
+  if (P->running && P->detached.load(std::memory_order_acquire)) {
+    const hipError_t q = hipStreamQuery(P->hs);
+    if (q == hipErrorNotReady) (void)hipGetLastError();
+    else (void)complete_run(P, q);
+  }
+  if (!P->running && !P->waiting.empty() && launch_run(P, lk) == RUN_LAUNCHED) {
+    P->detached.store(true, std::memory_order_release);
+    P->cv.notify_all();   // (threads that started to wait for this run while the look let go of the mutex: it is theirs to complete)
+  }
+}
+// frames of [outRead, outKnown) the host holds (a failed handle's counts may be ahead of them)
+static int64_t held_frames(sonicStream s) {
+  const int64_t n = s->outKnown - s->outRead;
+  const int64_t held = (int64_t)((s->hostOut.size() - std::min(s->hostHead, s->hostOut.size())) / (size_t)s->channels);
+  return std::max<int64_t>(0, std::min(n, held));
+}
 
 int spx_pool_write(sonicStream s, const short* in, int sampleCount) {
   SpxPool* P = pool_of(s);
   std::unique_lock<std::mutex> lk(P->mu);
-  enter(P, s, lk);
+  enter(P, s, lk, /*stage_only=*/true);
   if (spx_stream_failed(s)) return 0;
   if (s->pendingFlush && (!settle_locked(P, s, lk) || spx_stream_failed(s))) return 0;   // a write behind a staged flush is the next job
   if (s->nIn + sampleCount + s->tsmShift >= (1ll << 30)) {
@@ -709,10 +802,11 @@ int spx_pool_write(sonicStream s, const short* in, int sampleCount) {
 int spx_pool_flush(sonicStream s) {
   SpxPool* P = pool_of(s);
   std::unique_lock<std::mutex> lk(P->mu);
-  enter(P, s, lk);
+  enter(P, s, lk, /*stage_only=*/true);
   if (spx_stream_failed(s)) return 0;
   if (s->pendingFlush && (!settle_locked(P, s, lk) || spx_stream_failed(s))) return 0;
   s->pendingFlush = true;
+  s->flushWait = s->readyReads;
   enlist(P, s);
   return 1;
 }
@@ -728,15 +822,16 @@ bool spx_pool_sync(sonicStream s) {
 int spx_pool_read(sonicStream s, short* out, int bufferSize) {
   SpxPool* P = pool_of(s);
   std::unique_lock<std::mutex> lk(P->mu);
-  enter(P, s, lk);
-  if (s->poolPending) (void)settle_locked(P, s, lk);
+  if (s->readyReads) {
+    ready_step(P, s, lk);
+  } else {
+    enter(P, s, lk);
+    if (s->poolPending) (void)settle_locked(P, s, lk);
+  }
   (void)spx_stream_failed(s);   // (what the host holds is still delivered; the reason is this thread's last error)
-  int64_t n = s->outKnown - s->outRead;
+  int64_t n = held_frames(s);
   if (n <= 0 || bufferSize <= 0) return 0;
   if (n > bufferSize) n = bufferSize;
-  const int64_t held = (int64_t)((s->hostOut.size() - std::min(s->hostHead, s->hostOut.size())) / (size_t)s->channels);
-  if (n > held) n = held;   // (a failed handle's counts may be ahead of what the host holds)
-  if (n <= 0) return 0;
   const size_t cnt = (size_t)n * s->channels;
   memcpy(out, s->hostOut.data() + s->hostHead, cnt * sizeof(short));
   s->hostHead += cnt;
@@ -747,6 +842,14 @@ int spx_pool_read(sonicStream s, short* out, int bufferSize) {
     s->hostHead = 0;
   }
   return (int)n;
+}
+
+int spx_pool_available(sonicStream s) {
+  SpxPool* P = pool_of(s);
+  std::unique_lock<std::mutex> lk(P->mu);
+  ready_step(P, s, lk);
+  (void)spx_stream_failed(s);
+  return (int)held_frames(s);
 }
 
 // The stream gets a launch sequence of its own from here on (sonic2_api.hip): what waits is run, the frame records move
@@ -795,15 +898,15 @@ void spx_pool_forget(sonicStream s) {
     if (P->waiting.empty()) { P->hInUsed = 0; P->waitingSegs = 0; }
   }
   arena_release(P, s);
-  for (SlideBuf<int16_t>* b : {&s->dIn, &s->dOut})   // (nothing of a pooled handle is in flight between runs)
+  for (SlideBuf<int16_t>* b : {&s->dIn, &s->dOut})   // (no run is in flight: the loop above completed it)
     if (b->block) { block_free_locked(P, b->p - b->guard, b->block); b->p = nullptr; b->cap = 0; b->block = 0; }
   s->pooled = false;
 }
 
 extern "C" {
-// Coalesced execution of plain handles (default on; SPX_NO_POOL=1 in the environment switches it off): applies to handles
-// created afterwards.
-void speedyHipSetCoalescing(int on) { g_coalesce.store(on ? 1 : 0); }
+// Coalesced execution of plain handles (default on; SPX_NO_POOL=1 in the environment switches it off, SPX_POOL_READY=1 makes it
+// coalesced with ready reads, 2): applies to handles created afterwards.
+void speedyHipSetCoalescing(int on) { g_coalesce.store(on == SPEEDY_HIP_COALESCE_READY ? SPEEDY_HIP_COALESCE_READY : on ? 1 : 0); }
 int speedyHipGetCoalescing(void) { return coalesce_default(); }
 // Launch sequences run and jobs served by the current device's pool so far (jobs / runs = handles per launch sequence).
 void speedyHipPoolStats(unsigned long long* runs, unsigned long long* jobs) {

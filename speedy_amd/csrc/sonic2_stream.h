@@ -167,11 +167,18 @@ struct sonicStreamStruct {  // speedyConnectionStruct + the parts of libsonic's 
 
   // ---- coalesced execution (sonic2_pool.hip).  A handle starts in its device's pool and stays there while nothing it
   // does needs a launch sequence of its own (callbacks, rate stage, sonicInt* calls, a change of mode inside the stream);
-  // leaving is one-way.  A pooled handle has no work in flight between API calls: writes and flushes are staged on the
-  // host, the pool runs them for all waiting handles in one launch sequence, synchronously.
+  // leaving is one-way.  Writes and flushes are staged on the host, the pool runs them for all waiting handles in one
+  // launch sequence.  A pooled handle in the default mode has no work in flight between API calls: the call that needs a
+  // result runs (or waits for) that sequence and completes it before it returns.  A READY-READS handle (readyReads,
+  // SPEEDY_HIP_COALESCE_READY) may: its reads launch what is staged and return without waiting, so a run that holds it
+  // can still be in flight -- "detached", nobody waiting on it -- when the call returns; whoever needs it over first
+  // completes it (sonic2_pool.hip wait_for_run).  Every call that touches the handle's device state (a setter, a second
+  // flush, leaving the pool, destruction) completes that run first.
   bool pooled = false;
+  bool readyReads = false;      // SPEEDY_HIP_COALESCE_READY: reads return what the host holds, never wait (but after a flush)
+  bool flushWait = false;       // ready reads: a flush was staged; the next read waits until everything up to it is delivered
   bool poolPending = false;     // on the pool's waiting list
-  bool inRun = false;           // part of the pool's run in flight: every call on the handle waits for that run (pool mutex)
+  bool inRun = false;           // part of the pool's run in flight: the handle's device state is the run's until it completes
   bool pendingFlush = false;    // ... with a flush behind the staged writes
   int64_t devIn = 0;            // frames of input that have reached dIn (nIn counts the staged ones too)
   struct Seg { int64_t pos; size_t src_off; int64_t frames; };   // staged write: stream position, offset in the pool's pinned input area
@@ -190,6 +197,7 @@ struct SpxJobPlan {
   SpxStreamDev JA, JW;       // the analysis / tension kernels' view and the walk kernel's (they differ on mixed streams)
   bool hasRing = false, nonlinear = false, taps = false, speedupKernel = false, flush = false, direct = false;
   int64_t T = 0, fa = 0, need = 0, handedAfter = 0;
+  int64_t nIn = 0;           // frames written when the job was formed (a ready-reads handle may stage more before it completes)
   int oldR = 0, newR = 0;
   int tiles = 0;             // analysis tiles of this job (plan tile size)
   SlideBuf<int16_t>* tsmIn = nullptr;
@@ -215,14 +223,17 @@ inline bool spx_stream_failed(sonicStream s) {
 bool spx_settings_ok(sonicStream s);
 
 // ---- sonic2_pool.hip ----
-SpxPool* spx_pool_for_device(int device, int coalesce = -1);   // nullptr when coalescing is off (coalesce: -1 the process default, 0 / 1 this handle's own choice)
-void spx_pool_adopt(SpxPool* pool, sonicStream s);     // at creation
+// coalesce: -1 the process default, 0 / 1 / 2 (SPEEDY_HIP_COALESCE_READY) this handle's own choice; the mode it resolves to
+int spx_pool_mode(int coalesce);
+SpxPool* spx_pool_for_device(int device, int coalesce = -1);   // nullptr when coalescing is off
+void spx_pool_adopt(SpxPool* pool, sonicStream s, bool ready);   // at creation
 int spx_pool_write(sonicStream s, const short* in, int sampleCount);   // stage a write
 int spx_pool_flush(sonicStream s);                                     // stage a flush
 bool spx_pool_sync(sonicStream s);                     // run everything that waits (if s waits); false: s has failed
 bool spx_pool_leave(sonicStream s);                    // hand the stream to the eager path (runs what waits first)
 void spx_pool_forget(sonicStream s);                   // at destruction: off the lists, arena slots returned
 int spx_pool_read(sonicStream s, short* out, int bufferSize);
+int spx_pool_available(sonicStream s);                 // a ready-reads handle's sonicSamplesAvailable (the read's rules, no copy)
 // frame-arena slide of a pooled handle's records: make [keep, hi) addressable, keeping [keep, filled)
 bool spx_pool_slide_frames(SpxPool* pool, sonicStream s, int64_t keep, int64_t hi, int64_t filled, SpxDeferred* defer);
 const SpxFrameRec* spx_pool_arena_rec(SpxPool* pool);

@@ -9,11 +9,20 @@ from ._lib import FEATURES_FN, TENSION_FN, c_float_p, c_short_p, lib
 
 class SonicStream:
     def __init__(self, sample_rate, channels, match_matlab=False, coalesce=None):
-        """coalesce: None = the process-wide default (speedyHipSetCoalescing / SPX_NO_POOL), False = this handle runs its
-        own launch sequence per write, True = coalesced.  The choice is per handle; no process-wide switch is touched."""
+        """coalesce: None = the process-wide default (speedyHipSetCoalescing / SPX_NO_POOL / SPX_POOL_READY), False = this
+        handle runs its own launch sequence per write, True = coalesced, "ready" = coalesced with ready reads (reads return
+        what is already on the host and never wait for the GPU, but after a flush; sonic2.h SPEEDY_HIP_COALESCE_READY).
+        The choice is per handle; no process-wide switch is touched."""
         self.L = lib()
-        self.h = self.L.speedyHipCreateSonicStreamEx(int(sample_rate), int(channels), int(bool(match_matlab)),
-                                                     -1 if coalesce is None else int(bool(coalesce)))
+        if coalesce is None:
+            mode = -1
+        elif isinstance(coalesce, str):
+            if coalesce != "ready":
+                raise ValueError("coalesce: None, a bool or \"ready\", not %r" % coalesce)
+            mode = 2
+        else:
+            mode = int(bool(coalesce))
+        self.h = self.L.speedyHipCreateSonicStreamEx(int(sample_rate), int(channels), int(bool(match_matlab)), mode)
         if not self.h:
             raise RuntimeError("sonicCreateStream: " + self.L.speedyHipLastError().decode())
         self.channels = channels

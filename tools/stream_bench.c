@@ -2,13 +2,18 @@
  * throughput of the drop-in API.  Every round writes `chunk` frames to each handle and then reads from each -- the
  * reference CLI's loop (speedy_wave.cc:199-231) turned sideways, as a server with N live streams runs it.
  *
- *   stream_bench STREAMS [SECONDS=10] [CHUNK=1000] [SPEED=3.5] [NONLINEAR=1] [ORDER=rounds|percall|threads:T] [RATE=16000]
+ *   stream_bench STREAMS [SECONDS=10] [CHUNK=1000] [SPEED=3.5] [NONLINEAR=1] [ORDER=rounds|percall|threads:T][:ready] [RATE=16000]
  *
  * ORDER=percall reads right after each write, handle by handle -- the reference's own call order (speedy_wave.cc:199-220,
  * sonic_test.cc:384-392) on one thread: one launch sequence per handle per write.
  * ORDER=threads:T (round 6): T host threads, each with STREAMS / T handles of its own, each running that same write -> read loop
  * over its handles -- a server's shape for an API whose streams are independent but not thread-safe (sonic2.h:54-84).  The
  * library combines what the threads stage into common launch sequences (sonic2_pool.hip, flat combining).
+ * ORDER=...:ready (percall:ready, threads:T:ready, rounds:ready): the same loops on handles created with
+ * SPEEDY_HIP_COALESCE_READY (sonic2.h): a read returns what is already on the host and never waits for the GPU (but after the
+ * flush), so a launch sequence carries every write staged while the previous one ran.  The audio is the same: "crc" hashes
+ * every frame each handle delivers over its life (warm-up and drain included), handle by handle, so it does not depend on how
+ * the frames were split between reads -- a ready run and a blocking run of the same arguments print the same crc and frames_out.
  * Prints one line of JSON. */
 #include <math.h>
 #include <pthread.h>
@@ -45,13 +50,25 @@ static void synth(short* x, int n, int rate, unsigned seed) {
   }
 }
 
+/* per handle: frames delivered so far and a hash of every sample at its position -- independent of how the frames were split
+ * between reads (mono: one value per frame) */
+typedef struct { long long frames; unsigned long long hash; } audio_t;
+static void fold(audio_t* a, const short* o, int frames) {
+  unsigned long long h = a->hash;
+  const unsigned long long p = (unsigned long long)a->frames + 1u;
+  int k;
+  for (k = 0; k < frames; k++) h += ((unsigned long long)(unsigned short)o[k] + 1u) * ((p + (unsigned long long)k) * 0x9E3779B97F4A7C15ull);
+  a->hash = h;
+  a->frames += frames;
+}
+
 typedef struct {
   sonicStream* h;       /* this thread's handles */
+  audio_t* au;          /* ... and what they delivered */
   int n_h, first;       /* their number, index of the first (source selection) */
   short** src;
   int n_src, n, chunk;
-  long long total_out, rounds;
-  unsigned long long crc;
+  long long rounds;
   int failed;
   pthread_barrier_t* start;
 } worker_t;
@@ -67,14 +84,13 @@ static void* thread_main(void* arg) {
     for (i = 0; i < w->n_h; i++) {
       if (sonicWriteShortToStream(w->h[i], w->src[(w->first + i) % w->n_src] + pos, k) != 1) { w->failed = 1; free(out); return NULL; }
       got = sonicReadShortFromStream(w->h[i], out, w->chunk);
-      w->total_out += got;
-      if (got > 0) w->crc = w->crc * 1315423911ull + (unsigned short)out[got - 1];
+      fold(&w->au[i], out, got);
     }
     w->rounds++;
   }
   for (i = 0; i < w->n_h; i++) sonicFlushStream(w->h[i]);
   for (i = 0; i < w->n_h; i++)
-    while ((got = sonicReadShortFromStream(w->h[i], out, 8192)) > 0) w->total_out += got;
+    while ((got = sonicReadShortFromStream(w->h[i], out, 8192)) > 0) fold(&w->au[i], out, got);
   free(out);
   return NULL;
 }
@@ -85,25 +101,29 @@ int main(int argc, char** argv) {
   const int chunk = argc > 3 ? atoi(argv[3]) : 1000;
   const float speed = argc > 4 ? (float)atof(argv[4]) : 3.5f;
   const float nonlinear = argc > 5 ? (float)atof(argv[5]) : 1.0f;
-  const int percall = argc > 6 && strcmp(argv[6], "percall") == 0;
-  const int threads = (argc > 6 && strncmp(argv[6], "threads:", 8) == 0) ? atoi(argv[6] + 8) : 0;
+  const char* order = argc > 6 ? argv[6] : "rounds";
+  const size_t olen = strlen(order);
+  const int ready = olen >= 6 && strcmp(order + olen - 6, ":ready") == 0;
+  const int percall = strncmp(order, "percall", 7) == 0;
+  const int threads = strncmp(order, "threads:", 8) == 0 ? atoi(order + 8) : 0;
   const int rate = argc > 7 ? atoi(argv[7]) : 16000;
   const int n = (int)(seconds * rate);
   const int n_src = 8;
   short* src[8];
   sonicStream* h = (sonicStream*)calloc((size_t)streams, sizeof(sonicStream));
+  audio_t* au = (audio_t*)calloc((size_t)streams, sizeof(audio_t));
   short* out = (short*)malloc(sizeof(short) * (size_t)(chunk > 8192 ? chunk : 8192));
   long long total_out = 0, rounds = 0;
   unsigned long long crc = 0;
   double t0, t1, worst = 0.0;
   int i, pos;
-  if (streams < 1 || n < 1 || chunk < 1 || !h || !out) return 2;
+  if (streams < 1 || n < 1 || chunk < 1 || !h || !au || !out) return 2;
   for (i = 0; i < n_src; i++) {
     src[i] = (short*)malloc(sizeof(short) * (size_t)n);
     synth(src[i], n, rate, 17u + (unsigned)i);
   }
   for (i = 0; i < streams; i++) {
-    h[i] = sonicCreateStream(rate, 1);
+    h[i] = ready ? speedyHipCreateSonicStreamEx(rate, 1, 0, SPEEDY_HIP_COALESCE_READY) : sonicCreateStream(rate, 1);
     if (!h[i]) { fprintf(stderr, "sonicCreateStream: %s\n", speedyHipLastError()); return 1; }
     sonicSetSpeed(h[i], speed);
     sonicEnableNonlinearSpeedup(h[i], nonlinear);
@@ -111,8 +131,7 @@ int main(int argc, char** argv) {
   }
   /* one warm-up round on every handle (plans, pinned areas, code objects), not timed */
   for (i = 0; i < streams; i++) sonicWriteShortToStream(h[i], src[i % n_src], chunk < n ? chunk : n);
-  for (i = 0; i < streams; i++) total_out += sonicReadShortFromStream(h[i], out, 8192);
-  total_out = 0;
+  for (i = 0; i < streams; i++) fold(&au[i], out, sonicReadShortFromStream(h[i], out, 8192));
   if (threads > 0) {
     const int T = threads < streams ? threads : streams;
     pthread_t* th = (pthread_t*)calloc((size_t)T, sizeof(pthread_t));
@@ -122,25 +141,27 @@ int main(int argc, char** argv) {
     pthread_barrier_init(&start, NULL, (unsigned)T + 1u);
     for (t = 0; t < T; t++) {
       const int a = (int)((long long)streams * t / T), b = (int)((long long)streams * (t + 1) / T);
-      w[t].h = h + a; w[t].n_h = b - a; w[t].first = a; w[t].src = src; w[t].n_src = n_src; w[t].n = n; w[t].chunk = chunk;
-      w[t].start = &start;
+      w[t].h = h + a; w[t].au = au + a; w[t].n_h = b - a; w[t].first = a; w[t].src = src; w[t].n_src = n_src; w[t].n = n;
+      w[t].chunk = chunk; w[t].start = &start;
       if (pthread_create(&th[t], NULL, thread_main, &w[t]) != 0) { fprintf(stderr, "pthread_create failed\n"); return 1; }
     }
     pthread_barrier_wait(&start);
     t0 = now_s();
     for (t = 0; t < T; t++) pthread_join(th[t], NULL);
     t1 = now_s();
-    for (t = 0; t < T; t++) { total_out += w[t].total_out; crc ^= w[t].crc * (unsigned long long)(t + 1); bad |= w[t].failed; if (w[t].rounds > rounds) rounds = w[t].rounds; }
+    for (t = 0; t < T; t++) { bad |= w[t].failed; if (w[t].rounds > rounds) rounds = w[t].rounds; }
     if (bad) { fprintf(stderr, "a thread's write failed: %s\n", speedyHipLastError()); return 1; }
+    for (i = 0; i < streams; i++) { total_out += au[i].frames; crc = crc * 1315423911ull + au[i].hash + (unsigned long long)au[i].frames; }
     {
       const double dt = t1 - t0, in_frames = (double)streams * (double)(n - chunk);
       unsigned long long runs = 0, jobs = 0;
       speedyHipPoolStats(&runs, &jobs);
       printf("{\"streams\": %d, \"threads\": %d, \"rate\": %d, \"seconds_each\": %.1f, \"chunk\": %d, \"speed\": %.2f, \"nonlinear\": %.2f, "
-             "\"order\": \"threads\", \"wall_s\": %.4f, \"msamples_per_s\": %.2f, \"x_realtime_per_stream\": %.1f, "
+             "\"order\": \"%s\", \"ready\": %d, \"wall_s\": %.4f, \"msamples_per_s\": %.2f, \"x_realtime_per_stream\": %.1f, "
              "\"us_per_round\": %.1f, \"frames_out\": %lld, \"launch_sequences\": %llu, \"handles_per_sequence\": %.1f, \"crc\": %llu}\n",
-             streams, T, rate, seconds, chunk, speed, nonlinear, dt, in_frames / dt * 1e-6, ((double)(n - chunk) / rate) / dt,
-             dt / (double)(rounds ? rounds : 1) * 1e6, total_out, runs, runs ? (double)jobs / (double)runs : 0.0, crc);
+             streams, T, rate, seconds, chunk, speed, nonlinear, ready ? "threads:ready" : "threads", ready, dt, in_frames / dt * 1e-6,
+             ((double)(n - chunk) / rate) / dt, dt / (double)(rounds ? rounds : 1) * 1e6, total_out, runs,
+             runs ? (double)jobs / (double)runs : 0.0, crc);
     }
     for (i = 0; i < streams; i++) sonicDestroyStream(h[i]);
     return 0;
@@ -152,20 +173,13 @@ int main(int argc, char** argv) {
     double r1;
     if (percall) {
       for (i = 0; i < streams; i++) {
-        int got;
         if (sonicWriteShortToStream(h[i], src[i % n_src] + pos, w) != 1) { fprintf(stderr, "write: %s\n", speedyHipLastError()); return 1; }
-        got = sonicReadShortFromStream(h[i], out, chunk);
-        total_out += got;
-        if (got > 0) crc = crc * 1315423911ull + (unsigned short)out[got - 1];
+        fold(&au[i], out, sonicReadShortFromStream(h[i], out, chunk));
       }
     } else {
       for (i = 0; i < streams; i++)
         if (sonicWriteShortToStream(h[i], src[i % n_src] + pos, w) != 1) { fprintf(stderr, "write: %s\n", speedyHipLastError()); return 1; }
-      for (i = 0; i < streams; i++) {
-        const int got = sonicReadShortFromStream(h[i], out, chunk);
-        total_out += got;
-        if (got > 0) crc = crc * 1315423911ull + (unsigned short)out[got - 1];
-      }
+      for (i = 0; i < streams; i++) fold(&au[i], out, sonicReadShortFromStream(h[i], out, chunk));
     }
     r1 = now_s() - r0;
     if (r1 > worst) worst = r1;
@@ -174,20 +188,21 @@ int main(int argc, char** argv) {
   for (i = 0; i < streams; i++) sonicFlushStream(h[i]);
   for (i = 0; i < streams; i++) {
     int got;
-    while ((got = sonicReadShortFromStream(h[i], out, 8192)) > 0) total_out += got;
+    while ((got = sonicReadShortFromStream(h[i], out, 8192)) > 0) fold(&au[i], out, got);
   }
   t1 = now_s();
+  for (i = 0; i < streams; i++) { total_out += au[i].frames; crc = crc * 1315423911ull + au[i].hash + (unsigned long long)au[i].frames; }
   {
     const double dt = t1 - t0, in_frames = (double)streams * (double)(n - chunk);
     unsigned long long runs = 0, jobs = 0;
     speedyHipPoolStats(&runs, &jobs);
     printf("{\"streams\": %d, \"rate\": %d, \"seconds_each\": %.1f, \"chunk\": %d, \"speed\": %.2f, \"nonlinear\": %.2f, "
-           "\"order\": \"%s\", \"wall_s\": %.4f, \"msamples_per_s\": %.2f, \"x_realtime_per_stream\": %.1f, "
+           "\"order\": \"%s%s\", \"ready\": %d, \"wall_s\": %.4f, \"msamples_per_s\": %.2f, \"x_realtime_per_stream\": %.1f, "
            "\"us_per_round\": %.1f, \"worst_round_us\": %.1f, \"frames_out\": %lld, \"launch_sequences\": %llu, "
            "\"handles_per_sequence\": %.1f, \"crc\": %llu}\n",
-           streams, rate, seconds, chunk, speed, nonlinear, percall ? "percall" : "rounds", dt, in_frames / dt * 1e-6,
-           ((double)(n - chunk) / rate) / dt, dt / (double)(rounds ? rounds : 1) * 1e6, worst * 1e6, total_out, runs,
-           runs ? (double)jobs / (double)runs : 0.0, crc);
+           streams, rate, seconds, chunk, speed, nonlinear, percall ? "percall" : "rounds", ready ? ":ready" : "", ready, dt,
+           in_frames / dt * 1e-6, ((double)(n - chunk) / rate) / dt, dt / (double)(rounds ? rounds : 1) * 1e6, worst * 1e6,
+           total_out, runs, runs ? (double)jobs / (double)runs : 0.0, crc);
   }
   for (i = 0; i < streams; i++) sonicDestroyStream(h[i]);
   return 0;
