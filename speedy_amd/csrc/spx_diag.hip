@@ -64,7 +64,8 @@ int spx_debug_walk_info(int sample_rate, int channels, int n_streams, int speedu
   out[4] = c.waves;
   return 0;
 }
-// ... and the same for the analysis kernel of a rate (out[0] VGPRs, out[1] scratch bytes, out[2] LDS bytes) and the tension kernel
+// ... and the same for the analysis kernel of a rate (out[0] VGPRs, out[1] scratch bytes, out[2] LDS bytes, out[3] the plan's
+// transforming waves, SpxPlanDev::dft_waves) and the tension kernel
 int spx_debug_analysis_info(int sample_rate, int* out) {
   const SpxPlanDev* P = spx_internal_shared_plan(sample_rate, 0);
   if (!P || !out) return -1;
@@ -72,6 +73,7 @@ int spx_debug_analysis_info(int sample_rate, int* out) {
   out[0] = spx_analysis_vgprs(*P, &scratch);
   out[1] = scratch;
   out[2] = (int)spx_analysis_lds_bytes(*P);
+  out[3] = P->dft_waves;
   return 0;
 }
 

@@ -592,12 +592,13 @@ def test_many_channels(orc, rate, ch):
         assert np.array_equal(outs[0], ref["out"]), (rate, ch, speed, nl)
 
 
-@pytest.mark.parametrize("rate", [1000, 3999, 4001, 7919, 12345, 24000, 37800, 50000, 60000, 62000, 88200, 96000, 127999])
+@pytest.mark.parametrize("rate", [1000, 3999, 4001, 6467, 7919, 12345, 24000, 37800, 50000, 60000, 62000, 88200, 96000, 127999])
 def test_unusual_sample_rates(orc, rate):
-    """Rates nobody tunes for: below the 4 kHz decimation threshold (skip = 1), prime window lengths (generic and Rader
-    DFT stages), the range above 49 kHz where the plan falls back to the 8-frame analysis tile, and (round 3) the range
-    above 61 kHz -- the reference takes any rate, speedy.c:213 -- where two waves, then one, transform 4-frame tiles.
-    Mono and stereo, linear and nonlinear, taps included."""
+    """Rates nobody tunes for: below the 4 kHz decimation threshold (skip = 1), prime window lengths (W = 59 at 3 999 Hz
+    through the generic odd-prime stage, W = 97 at 6 467 Hz through Rader's algorithm in the plan-driven kernel), the range
+    above 49 kHz where the plan falls back to the 8-frame analysis tile, and (round 3) the range above 61 kHz -- the
+    reference takes any rate, speedy.c:213 -- where two waves, then one, transform 4-frame tiles.  Mono and stereo, linear
+    and nonlinear, taps included."""
     from speedy_amd.batch import compress_batch
     from speedy_amd.synth import speech_like
     for ch in (1, 2):
@@ -891,7 +892,7 @@ def test_kernel_resources_of_every_form_the_engine_selects():
         got = list(out)
         assert got[3] == form, ((rate, ch, n, short, lean), got)
         assert 0 < got[0] <= vg and 0 <= got[1] <= sc, ((rate, ch, n, short, lean), got, (vg, sc))
-    a = (C.c_int * 3)()
+    a = (C.c_int * 4)()
     # (22.05 kHz: since the fused transform of round 5 the 16-frame instantiation keeps seven dwords in scratch at its 168 registers --
     # three waves per SIMD -- and is 5 % faster all the same, profiles/r05/r5i_dft_ab.txt)
     for rate, vg, sc in ((16000, 128, 0), (22050, 168, 28), (44100, 256, 0), (48000, 256, 0), (32000, 160, 0), (24000, 136, 0), (8000, 88, 0),
