@@ -90,6 +90,26 @@ int spx_batch_run(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, co
                   int16_t* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
                   const spx_taps* taps, void* hip_stream);
 
+/* spx_batch_run with a PLAYBACK RATE per stream: sonicSetRate before the first write (sonic2.h:70; the reference forwards it to
+ * the TSM dependency, whose adjustRate resamples what the speed stage produced, soniclib.c:169-175).
+ *   rates  HOST float[n_streams], NULL = every rate 1 (the call IS spx_batch_run then, as it is with every entry 1).
+ * out / n_out hold the FINAL frames -- behind the rate stage -- and out_cap counts final frames (spx_plan_out_capacity_rate);
+ * n_out[i] negative = out_cap was too small (nothing is written past out_off + out_cap * channels).  A job with rates[i] == 1 gets
+ * the bytes and the count spx_batch_run gives it, in the same call as jobs with other rates.  Taps are spx_batch_run's (the rate
+ * stage lies behind everything they observe); spx_batch_pack_outputs and spx_batch_read_steps work on the result unchanged.
+ * A rate <= 0, not finite, or so large that (int)(sample rate / rate) < 1 is refused: -1, spx_last_error, nothing launched.
+ * The workspace (spx_batch_workspace_bytes_rate) also holds the speed stage's output of the jobs with a rate other than 1.
+ * Asynchronous on hip_stream like spx_batch_run, kernels in sequence; the plain call only (no _ahead / _overlapped / _mixed form,
+ * no pipeline object).  Any channel count the walk kernel's window takes: the 16 of the streaming API's rate
+ * stage do not apply. */
+int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, const int16_t* in,
+                       int16_t* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
+                       const spx_taps* taps, void* hip_stream);
+/* 0 (spx_last_error) for a rate spx_batch_run_rate would refuse. */
+size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams);
+/* spx_plan_out_capacity_for behind the rate stage: safe capacity in FINAL frames; -1 (spx_last_error) for a rate that is refused. */
+int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate);
+
 /* spx_batch_run for a caller that issues batch after batch (round 4): consecutive calls are software-pipelined.  This call's
  * analysis and tension kernels are enqueued on a stream of the library's and start AT ONCE -- beside the walk kernel of the
  * previous call, which is still running on hip_stream -- and its own walk kernel follows on hip_stream with every speed ready.
@@ -285,6 +305,8 @@ int spx_debug_log_check(unsigned first_block, unsigned end_block, unsigned long 
 int spx_debug_last_call_concurrent(void);
 /* Sum over the same calls of the frame-rate (tension) kernel's time, as of the last spx_timing_collect. */
 double spx_timing_last_tension_ms(void);
+/* ... and of the rate kernel's (spx_batch_run_rate calls with a rate other than 1). */
+double spx_timing_last_rate_ms(void);
 
 /* Diagnostics: the number of pitch searches (libsonic's findPitchPeriod calls) each stream's walk has run since the stream started (a batch job starts it) -- the length of the stream's chain of dependent steps, which is what bounds a call with one stream per CU.
  *   workspace  DEVICE  the workspace that call ran with;  steps  HOST  int32[n_streams].  Waits for hip_stream first. */

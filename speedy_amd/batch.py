@@ -1,4 +1,5 @@
-"""Batch engine: N independent streams, device-resident, one spx_batch_run call (include/speedy_hip.h).
+"""Batch engine: N independent streams, device-resident, one spx_batch_run call (include/speedy_hip.h) -- or, with a playback
+rate per stream (sonicSetRate before the first write), one spx_batch_run_rate call.
 
 Host-side mirror of what the reference's caller loop does per stream (speedy_wave.cc:154-242): create,
 setSpeed, enableNonlinear, setFeedback, write everything, flush, drain."""
@@ -28,8 +29,13 @@ class Plan:
     def frames(self, n_in):
         return self.L.spx_plan_frames(self.h, int(n_in))
 
-    def out_capacity(self, n_in, speed, nonlinear=1.0):
-        return self.L.spx_plan_out_capacity_for(self.h, int(n_in), float(speed), float(nonlinear))
+    def out_capacity(self, n_in, speed, nonlinear=1.0, rate=None):
+        if rate is None:
+            return self.L.spx_plan_out_capacity_for(self.h, int(n_in), float(speed), float(nonlinear))
+        cap = self.L.spx_plan_out_capacity_rate(self.h, int(n_in), float(speed), float(nonlinear), float(rate))
+        if cap < 0:
+            raise RuntimeError("spx_plan_out_capacity_rate: " + self.L.spx_last_error().decode())
+        return cap
 
     def close(self):
         if self.h:
@@ -38,13 +44,20 @@ class Plan:
 
 
 class Batch:
-    """A prepared batch: inputs packed into one HBM buffer, outputs and workspace allocated once."""
+    """A prepared batch: inputs packed into one HBM buffer, outputs and workspace allocated once.
+    rate: a playback rate (sonicSetRate) for every stream or one per stream -- run() is then spx_batch_run_rate and the
+    outputs are the final frames behind the rate stage; None: spx_batch_run, call for call as before."""
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
-                 spectrogram_taps=False):
+                 spectrogram_taps=False, rate=None):
         self.plan = plan
         n = len(lengths)
         self.n = n
+        self.rates = None
+        if rate is not None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
+            self.rates = np.ascontiguousarray(np.broadcast_to(np.asarray(rate, np.float32), (n,)))
         ch = np.broadcast_to(np.asarray(channels, np.int32), (n,)).copy()
         sp = np.broadcast_to(np.asarray(speed, np.float32), (n,)).copy()
         nlv = np.broadcast_to(np.asarray(nonlinear, np.float32), (n,)).copy()
@@ -56,7 +69,8 @@ class Batch:
         self.in_offs, self.out_offs, self.out_caps, self.frame_offs, self.frames = [], [], [], [], []
         fo = 0
         for i in range(n):
-            cap = plan.out_capacity(int(self.lengths[i]), float(sp[i]), float(nlv[i]))
+            cap = plan.out_capacity(int(self.lengths[i]), float(sp[i]), float(nlv[i]),
+                                    None if self.rates is None else float(self.rates[i]))
             j = self.jobs[i]
             j.in_off, j.n_in, j.out_off, j.out_cap = in_off, int(self.lengths[i]), out_off, cap
             j.channels, j.speed, j.nonlinear, j.feedback = int(ch[i]), float(sp[i]), float(nlv[i]), float(fb[i])
@@ -75,7 +89,12 @@ class Batch:
         self.d_in = torch.zeros(max(1, in_off) + 64, dtype=torch.int16, device=dev)
         self.d_out = torch.zeros(max(1, out_off), dtype=torch.int16, device=dev)
         self.d_nout = torch.zeros(n, dtype=torch.int64, device=dev)
-        wsb = plan.L.spx_batch_workspace_bytes(plan.h, self.jobs, n)
+        if self.rates is None:
+            wsb = plan.L.spx_batch_workspace_bytes(plan.h, self.jobs, n)
+        else:
+            wsb = plan.L.spx_batch_workspace_bytes_rate(plan.h, self.jobs, self._rates_ptr(), n)
+            if wsb == 0:
+                raise RuntimeError("spx_batch_workspace_bytes_rate: " + plan.L.spx_last_error().decode())
         self.d_ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
         self.taps = None
         if taps:
@@ -100,9 +119,19 @@ class Batch:
             host[self.in_offs[i]:self.in_offs[i] + x.size] = x
         self.d_in.copy_(torch.from_numpy(host))
 
+    def _rates_ptr(self):
+        return self.rates.ctypes.data_as(C.POINTER(C.c_float))
+
     def run(self, stream=None):
-        """Enqueue the whole hot path (analysis + walk) for the batch on `stream` (torch stream or None)."""
+        """Enqueue the whole hot path (analysis + walk, and the rate stage of a batch with rates) on `stream` (torch stream or None)."""
         hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if self.rates is not None:
+            rc = self.plan.L.spx_batch_run_rate(self.plan.h, self.jobs, self._rates_ptr(), self.n, self.d_in.data_ptr(),
+                                                self.d_out.data_ptr(), self.d_nout.data_ptr(), self.d_ws.data_ptr(),
+                                                self.d_ws.numel(), C.byref(self.taps) if self.taps is not None else None, hs)
+            if rc != 0:
+                raise RuntimeError("spx_batch_run_rate: " + self.plan.L.spx_last_error().decode())
+            return
         rc = self.plan.L.spx_batch_run(self.plan.h, self.jobs, self.n, self.d_in.data_ptr(), self.d_out.data_ptr(),
                                        self.d_nout.data_ptr(), self.d_ws.data_ptr(), self.d_ws.numel(),
                                        C.byref(self.taps) if self.taps is not None else None, hs)
@@ -114,6 +143,8 @@ class Batch:
         two Batch objects).  in_ready: a recorded torch.cuda.Event behind whatever completes the input (None: the input is
         resident when the call is made).  overlap: spx_batch_run_overlapped -- the walk kernels of consecutive calls overlap
         too; nothing enqueued between two calls may touch the later call's buffers (include/speedy_hip.h)."""
+        if self.rates is not None:
+            raise RuntimeError("a batch with rates runs through the plain call only (spx_batch_run_rate)")
         hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
         if overlap:
             assert in_ready is None
@@ -437,12 +468,12 @@ class Pipeline:
 
 
 def compress_batch(streams, sample_rate, channels, speed, nonlinear=1.0, feedback=0.0, match_matlab=False,
-                   taps=False, spectrogram_taps=False):
-    """One-call convenience: returns (list of outputs, Batch)."""
+                   taps=False, spectrogram_taps=False, rate=None):
+    """One-call convenience: returns (list of outputs, Batch).  rate: sonicSetRate, one value or one per stream."""
     plan = Plan(sample_rate, match_matlab)
     ch = np.broadcast_to(np.asarray(channels, np.int32), (len(streams),))
     lengths = [np.asarray(x).size // int(c) for x, c in zip(streams, ch)]
-    b = Batch(plan, lengths, channels, speed, nonlinear, feedback, taps=taps, spectrogram_taps=spectrogram_taps)
+    b = Batch(plan, lengths, channels, speed, nonlinear, feedback, taps=taps, spectrogram_taps=spectrogram_taps, rate=rate)
     b.upload(streams)
     b.run()
     return b.results(), b

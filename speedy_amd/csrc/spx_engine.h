@@ -128,7 +128,7 @@ struct spx_plan {
 };
 
 // ---- process-wide state (spx_engine.hip) ----
-struct EvPair { hipEvent_t a, b; int kind; };  // kind 0 = analysis launch, 1 = walk launch, 2 = tension launch
+struct EvPair { hipEvent_t a, b; int kind; };  // kind 0 = analysis launch, 1 = walk launch, 2 = tension launch, 3 = rate launch (spx_batch_run_rate)
 extern std::atomic<bool> g_timing;
 extern std::atomic<int> g_last_concurrent;   // spx_debug_last_call_concurrent (2 = pipelined with the previous call)
 extern std::atomic<int> g_concurrent;        // spx_set_concurrent
@@ -182,8 +182,21 @@ struct SpxForce { int concurrent; bool idle_start; int total_streams; hipEvent_t
                   bool no_exclusive;   // the walk workgroups do NOT ask for a CU of their own and take the 4096-frame window (a mixed call whose walk
                                        // kernels overlap the previous call's: two calls' walk workgroups and an analysis workgroup on a CU)
 };
+// A call with a playback rate per stream (spx_batch_run_rate): jobs with rate != 1 go through the GENERAL walk kernel without the
+// flush truncation (SPX_F_NO_TRUNC) into a TSM buffer inside the workspace, and a batched rate kernel (spx_rate_batch.hip) behind
+// the walk kernel writes the caller's buffer.  Kernels in sequence on the caller's stream.
+struct SpxRateCall {
+  std::vector<int64_t> walk_out_off, walk_out_cap;   // per job: where the walk kernel writes (int16 values from `out`; may be negative)
+  std::vector<unsigned char> no_trunc;               // per job: rate != 1
+  std::vector<int> table;                            // the SpxRateJob records, as the staging kernel copies them (32-bit words)
+  SpxRateJob* d_table = nullptr;                     // DEVICE (workspace): the records, ...
+  int64_t* d_tsm_n = nullptr;                        // ... the walk kernel's counts
+  const int16_t* tsm_base = nullptr;                 // the base SpxRateJob::tsm_off counts from
+  int max_blocks = 1;
+};
 struct SpxCallOpts {
   const SpxForce* force = nullptr;
+  const SpxRateCall* rate = nullptr;   // spx_batch_run_rate with at least one rate != 1
   bool ahead_req = false;      // spx_batch_run_ahead: pipelined with the plan's previous call where the shape allows
   bool overlap_req = false;    // spx_batch_run_overlapped: ... and its walk kernel beside the previous call's
   void* in_ready = nullptr;    // hipEvent_t: the producers wait for it (the caller's "input is there")

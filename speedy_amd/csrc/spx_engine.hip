@@ -128,7 +128,7 @@ Layout layout_for(const SpxPlanDev& d, const spx_stream_job* jobs, int n) {
 // Job tables for `nch` consecutive time chunks of every stream: chunk c covers the input up to n_c frames
 // (n_c = n_in for the last chunk), starts where chunk c-1 stopped (frame_begin) and carries the state record.
 static int build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n, int nch,
-                         std::vector<SpxStreamDev>& v, std::vector<int>& tiles_per_chunk) {
+                         std::vector<SpxStreamDev>& v, std::vector<int>& tiles_per_chunk, const SpxRateCall* rc = nullptr) {
   v.resize((size_t)n * nch);
   tiles_per_chunk.assign(nch, 0);
   int64_t fo = 0;
@@ -160,6 +160,10 @@ static int build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n,
       s.n_frames = (int32_t)T;
       s.frame_begin = (int32_t)Tprev;
       s.flags = (c == 0 ? SPX_F_INIT : 0) | (c == nch - 1 ? SPX_F_FLUSH : 0);
+      if (rc) {   // a rate stage follows (spx_batch_run_rate): the walk kernel writes where the call says, untruncated where rate != 1
+        s.out_off = rc->walk_out_off[i]; s.out_cap = rc->walk_out_cap[i];
+        if (rc->no_trunc[i]) s.flags |= SPX_F_NO_TRUNC;
+      }
       s.frame_off = fo;
       s.first_tile = tiles_per_chunk[c];
       tiles_per_chunk[c] += (int)((T - Tprev + TF - 1) / TF);
@@ -458,7 +462,8 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   if (ws_bytes < L.total || !ws) return fail(-1, "spx_batch: workspace too small");
   const SpxSpeedClass SC = speed_class(jobs, n);
   const int maxC = SC.maxC;
-  const bool speedup_only = SC.speedup_only, any_speed = SC.any_speed;
+  // (a rate call: SPX_F_NO_TRUNC is the general walk kernel's -- neither speed-up form knows it -- so the whole call is the general kernel's)
+  const bool speedup_only = SC.speedup_only && !opt.rate, any_speed = SC.any_speed && !opt.rate;
   std::lock_guard<std::mutex> plan_lock(plan->mu);
   // a call that is not a sub-batch of run_split's leaves no split record for its workspace (spx_batch_analyze / _walk and mixed
   // calls come here directly: a stale record made spx_batch_read_steps look for sub-batch slices -- ADVICE r5)
@@ -484,7 +489,8 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   S.force_ahead = force && force->ahead_sa != nullptr;
   S.force_total_streams = force ? force->total_streams : n;
   S.ahead_req = opt.ahead_req; S.overlap_req = opt.overlap_req;
-  const SpxModeEnv E = mode_env();
+  SpxModeEnv E = mode_env();
+  if (opt.rate) E.concurrent_enabled = false;   // a rate call's kernels run in sequence on the caller's stream (the rate kernel ends it)
   SpxModeRuntime T;
   memset(&T, 0, sizeof(T));
   const int two_back = (plan->ahead_calls + SPX_RING - 2) % SPX_RING;
@@ -527,8 +533,9 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   // ---- execute ----
   std::vector<SpxStreamDev> sv;
   std::vector<int> tiles;
-  int rc = build_streams(d, jobs, n, nch, sv, tiles);
+  int rc = build_streams(d, jobs, n, nch, sv, tiles, opt.rate);
   if (rc) return rc;
+  if (opt.rate && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_rate: internal: not a plain call in sequence");
   unsigned char* w = static_cast<unsigned char*>(ws);
   SpxStreamDev* dstreams = reinterpret_cast<SpxStreamDev*>(w + L.off_streams);
   SpxStreamState* states = reinterpret_cast<SpxStreamState*>(w + L.off_states);
@@ -614,7 +621,8 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   // the staging kernel (same stream, nothing in between).
   const bool ahead_gate = ahead && !force && plan->ahead_started != nullptr && plan->ahead_n > 0 && !waited_prev &&
                           ring_previous_in_flight(plan);
-  rc = stage_tables(plan, sv, order, dstreams, d_order, d_flags, concurrent ? (unsigned)tiles[0] : 0u, d_ready,
+  // (a rate call is never concurrent: the tile order's place in the staging kernel carries its SpxRateJob records instead)
+  rc = stage_tables(plan, sv, opt.rate ? opt.rate->table : order, dstreams, opt.rate ? reinterpret_cast<int*>(opt.rate->d_table) : d_order, d_flags, concurrent ? (unsigned)tiles[0] : 0u, d_ready,
                     (concurrent || ahead) ? (unsigned)n + 1u : 0u, (ahead || chunk_ahead) ? sa : st, &staged_ev,
                     ahead_gate ? plan->ahead_started : nullptr, plan->ahead_n, 8000u);
   if (rc) return rc;
@@ -668,9 +676,13 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
         // AHEAD: the counts are all published by the time the kernel starts -- its one poll returns at once -- and its workgroups
         // count themselves in for the next call's gate.
         SpxTimed tm(timed, 1, stw);
-        spx_launch_walk(d, dj, n, maxC, in, out, n_out, states, scratch, (concurrent || ahead) ? d_ready : nullptr,
+        spx_launch_walk(d, dj, n, maxC, in, out, opt.rate ? opt.rate->d_tsm_n : n_out, states, scratch, (concurrent || ahead) ? d_ready : nullptr,
                         speedup_only, stw, false, (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, M.launch_lean, any_speed,
                         short_window_res || (!force && M.walk2 && !M.launch_lean && maxC > 1));
+      }
+      if (opt.rate && c == nch - 1) {   // the rate stage: TSM buffer -> the caller's out, final counts -> n_out
+        SpxTimed tm(timed, 3, stw);
+        spx_launch_rate_batch(opt.rate->d_table, n, opt.rate->max_blocks, states, opt.rate->d_tsm_n, opt.rate->tsm_base, out, n_out, stw);
       }
       if (M.ahead_forced && force->started_out) *force->started_out = d_ready + n;
       if (c == nch - 1 && !force) {
@@ -831,6 +843,109 @@ int spx_batch_walk(spx_plan_t plan, const spx_stream_job* jobs, int n, const int
   return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, false, true);
 }
 
+}  // extern "C"
+
+// ---- spx_batch_run_rate: a playback rate per stream (sonicSetRate before the first write) ----
+// The dependency's adjustRate works at newSampleRate / oldSampleRate with old = the sample rate and new = (int)(old / rate), both
+// halved until they fit 14 bits (sonic2_api.hip does the same for a handle).  0, or -1 with the streaming API's messages.
+static int rate_ratio(int sample_rate, float rate, int* old_rate, int* new_rate) {
+  if (!(rate > 0.0f) || !std::isfinite(rate)) return fail(-1, "sonicSetRate: rate must be finite and > 0");
+  const float q = sample_rate / rate;
+  if (!(q < 2147483520.0f)) return fail(-1, "sonicSetRate: rate too small for this sample rate");
+  int o = sample_rate, w = (int)q;
+  while (w > (1 << 14) || o > (1 << 14)) { w >>= 1; o >>= 1; }
+  if (w < 1) return fail(-1, "sonicSetRate: rate too large for this sample rate");
+  if (o < 1) return fail(-1, "sonicSetRate: rate too small for this sample rate");
+  *old_rate = o; *new_rate = w;
+  return 0;
+}
+// Frames the rate stage can make of m TSM frames: the k with floor(k * old / new) <= m - 2.
+static int64_t rate_frames(int64_t m, int old_rate, int new_rate) {
+  return m >= 2 ? ((m - 1) * (int64_t)new_rate + old_rate - 1) / old_rate : 0;
+}
+// Workspace of a rate call: the plain call's | SpxRateJob[n] | the walk kernel's counts | the TSM buffers of the jobs with rate != 1
+struct RateLayout { size_t off_table, off_tsm_n, off_tsm, total; std::vector<int64_t> tsm_off, tsm_cap; };
+static int rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, RateLayout& RL) {
+  size_t o = (spx_batch_workspace_bytes(plan, jobs, n) + 255) & ~(size_t)255;
+  RL.off_table = o; o += (sizeof(SpxRateJob) * (size_t)n + 255) & ~(size_t)255;
+  RL.off_tsm_n = o; o += (sizeof(int64_t) * (size_t)n + 255) & ~(size_t)255;
+  RL.off_tsm = o;
+  RL.tsm_off.assign(n, 0); RL.tsm_cap.assign(n, 0);
+  int64_t v = 0;
+  for (int i = 0; i < n; i++) {
+    if (rates[i] == 1.0f) continue;
+    if (jobs[i].channels < 1 || jobs[i].n_in < 0) return fail(-1, "spx_batch: bad job (channels < 1 or a negative count / offset)");
+    RL.tsm_off[i] = v;
+    RL.tsm_cap[i] = spx_internal_out_bound(plan->dev, jobs[i].n_in, jobs[i].speed, jobs[i].nonlinear != 0.0f);
+    v += (RL.tsm_cap[i] * jobs[i].channels + 7) & ~(int64_t)7;   // (every stream's buffer starts on a 16-byte boundary)
+  }
+  RL.total = o + sizeof(int16_t) * (size_t)v + 128;
+  return 0;
+}
+extern "C" {
+int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate) {
+  if (!plan) { fail(-1, "spx_plan_out_capacity_rate: bad arguments"); return -1; }
+  const int64_t cap = spx_internal_out_bound(plan->dev, n_in, speed, nonlinear != 0.0f);
+  if (rate == 1.0f) return cap;
+  int o = 1, w = 1;
+  if (rate_ratio(plan->dev.rate, rate, &o, &w)) return -1;
+  return rate_frames(cap, o, w) + 1;
+}
+size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams) {
+  if (!rates) return spx_batch_workspace_bytes(plan, jobs, n_streams);
+  if (!plan || !jobs || n_streams < 1) return 0;
+  for (int i = 0; i < n_streams; i++) { int o, w; if (rate_ratio(plan->dev.rate, rates[i], &o, &w)) return 0; }
+  RateLayout RL;
+  if (rate_layout(plan, jobs, rates, n_streams, RL)) return 0;
+  return RL.total;
+}
+int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
+                       int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
+  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+  bool any = false;
+  std::vector<int> oldR(n, 1), newR(n, 1);
+  if (rates)
+    for (int i = 0; i < n; i++) {
+      if (rate_ratio(plan->dev.rate, rates[i], &oldR[i], &newR[i])) return -1;   // (nothing is launched for a call that is refused)
+      any = any || rates[i] != 1.0f;
+    }
+  if (!any) return spx_batch_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs);
+  if (!in || !out || !n_out || !ws || (reinterpret_cast<uintptr_t>(out) & 1)) return fail(-1, "spx_batch_run_rate: bad arguments");
+  RateLayout RL;
+  if (rate_layout(plan, jobs, rates, n, RL)) return -1;
+  if (ws_bytes < RL.total) return fail(-1, "spx_batch_run_rate: workspace too small (spx_batch_workspace_bytes_rate)");
+  unsigned char* w = static_cast<unsigned char*>(ws);
+  SpxRateCall RC;
+  RC.d_table = reinterpret_cast<SpxRateJob*>(w + RL.off_table);
+  RC.d_tsm_n = reinterpret_cast<int64_t*>(w + RL.off_tsm_n);
+  RC.tsm_base = reinterpret_cast<const int16_t*>(w + RL.off_tsm);
+  // the walk kernel addresses its output from `out`: the TSM buffers' place counted from there (as the streaming API's pooled
+  // launches count theirs from a null base)
+  const int64_t tsm_from_out = (int64_t)((reinterpret_cast<intptr_t>(RC.tsm_base) - reinterpret_cast<intptr_t>(out)) / (intptr_t)sizeof(int16_t));
+  RC.walk_out_off.resize(n); RC.walk_out_cap.resize(n); RC.no_trunc.resize(n);
+  std::vector<SpxRateJob> tab((size_t)n);
+  memset(tab.data(), 0, sizeof(SpxRateJob) * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    const bool resample = rates[i] != 1.0f;
+    SpxRateJob& J = tab[i];
+    J.fin_off = jobs[i].out_off; J.fin_cap = jobs[i].out_cap;
+    J.channels = jobs[i].channels; J.old_rate = oldR[i]; J.new_rate = newR[i]; J.rate = rates[i];
+    J.bypass = resample ? 0 : 1;
+    J.tsm_off = RL.tsm_off[i]; J.tsm_cap = RL.tsm_cap[i];
+    J.n_blocks = 1;
+    if (resample && jobs[i].out_cap > 0) J.n_blocks = spx_rate_batch_blocks(std::min(jobs[i].out_cap, rate_frames(J.tsm_cap, J.old_rate, J.new_rate)), J.channels);
+    if (J.n_blocks > RC.max_blocks) RC.max_blocks = J.n_blocks;
+    RC.no_trunc[i] = resample ? 1 : 0;
+    RC.walk_out_off[i] = resample ? tsm_from_out + RL.tsm_off[i] : jobs[i].out_off;
+    RC.walk_out_cap[i] = resample ? RL.tsm_cap[i] : jobs[i].out_cap;
+  }
+  static_assert(sizeof(SpxRateJob) % sizeof(int) == 0, "the staging kernel copies 32-bit words");
+  RC.table.resize(sizeof(SpxRateJob) / sizeof(int) * (size_t)n);
+  memcpy(RC.table.data(), tab.data(), sizeof(SpxRateJob) * (size_t)n);
+  SpxCallOpts o;
+  o.rate = &RC;
+  return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, o);
+}
 }  // extern "C"
 // Pitch searches per stream of the batch's last run (SpxWalkState::steps): the length of every stream's dependent chain.
 // Waits for hip_stream, then copies the state records out of the workspace.

@@ -134,6 +134,26 @@ void spx_launch_rate(SpxRateState* rs, const SpxStreamState* st, const int64_t* 
                      int64_t fin_cap, int channels, int old_rate, int new_rate, float rate, int bypass, int flush,
                      hipStream_t hs);
 
+// Rate stage of a batch call (spx_batch_run_rate, spx_rate_batch.hip): every stream is one whole life cycle, so nothing is
+// carried -- one record per stream, written by the host, and a grid over (output block, stream).
+struct SpxRateJob {
+  int64_t tsm_off;    // the stream's TSM output (the walk kernel's, flush not truncated): first value, in int16 values from tsm_base
+  int64_t tsm_cap;    // ... and its capacity in frames
+  int64_t fin_off;    // the caller's out_off / out_cap: the final frames
+  int64_t fin_cap;
+  int32_t channels;
+  int32_t old_rate, new_rate;   // sample rate and (int)(sample rate / rate), both halved until they fit 14 bits
+  int32_t bypass;     // rate == 1: the walk kernel wrote the caller's buffer itself, only the count is handed on
+  float rate;
+  int32_t n_blocks;   // blocks that cover the most this stream can emit (known on the host); the grid's surplus blocks leave at once
+  int64_t pad_;
+};
+int spx_rate_batch_blocks(int64_t frames, int channels);
+// tsm_n: DEVICE, the walk kernel's counts (negative = the TSM buffer overflowed, SPX_NOUT_LOST_PRODUCER passes through);
+// n_out: DEVICE, the final counts (negative = fin_cap was too small).  Nothing is written past fin_off + fin_cap * channels.
+void spx_launch_rate_batch(const SpxRateJob* jobs, int n_streams, int max_blocks, const SpxStreamState* states, const int64_t* tsm_n,
+                           const int16_t* tsm_base, int16_t* fin_base, int64_t* n_out, hipStream_t hs);
+
 // Per-analysis-frame record written by the analysis kernel and consumed by the walk kernel.
 struct SpxFrameRec {
   float energy;  // sum_{i=1}^{N/2-1} s[i]^2, float, index order  (speedy.c:513-516 == :633-640)
