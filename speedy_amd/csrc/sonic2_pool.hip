@@ -583,8 +583,8 @@ static RunLaunch launch_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
     for (size_t i = g.i0; i < g.i1; i++) any_nl = any_nl || items[i].J.nonlinear;
     if (any_nl) spx_launch_tension(PL, dA + g.i0, ng, dStates + g.i0, P->aRec, P->aScr, no_taps, nullptr, nullptr, P->hs);
     lap(2);
-    spx_launch_walk(PL, dW + g.i0, ng, g.maxC, nullptr, nullptr, dNout + g.i0, dStates + g.i0, P->aScr, nullptr,
-                    items[g.i0].J.speedupKernel, P->hs, /*short_jobs=*/true);
+    spx_launch_walk(PL, {.n_streams = ng, .max_channels = g.maxC, .speedup_only = items[g.i0].J.speedupKernel, .short_jobs = true}, dW + g.i0,
+                    nullptr, nullptr, dNout + g.i0, dStates + g.i0, P->aScr, nullptr, 0, P->hs);
     lap(3);
   }
   const unsigned gy = (unsigned)std::min<int64_t>(64, std::max<int64_t>(1, (max_slice + 8191) / 8192));

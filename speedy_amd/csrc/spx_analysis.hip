@@ -1555,46 +1555,29 @@ extern "C" int spx_debug_log_check(unsigned first_block, unsigned end_block, uns
 #endif
 }
 
+// The one place that maps (frames per tile, compiled-in window; 0 = plan-driven) to an instantiation: the two launchers, the
+// register query and the kernel names (spx_diag.hip) all ask here.
+SpxKernelChoice spx_analysis_select(int tile_frames, int ctw) {
+#define AN_K(TFV, WV) SpxKernelChoice{"spx_analysis_kernel", reinterpret_cast<const void*>(spx_analysis_kernel<TFV, WV>), SPX_BLOCK, 2, {TFV, WV}}
+  static_assert(std::is_same<decltype(spx_analysis_kernel<SPX_TF_TINY, 0>), SpxAnalysisArgs>::value, "SpxAnalysisArgs is the kernel's argument list");
+  if (tile_frames == SPX_TF_TINY) return AN_K(SPX_TF_TINY, 0);
+  if (tile_frames == SPX_TF_SMALL)
+    return ctw == 240 ? AN_K(SPX_TF_SMALL, 240) : ctw == 330 ? AN_K(SPX_TF_SMALL, 330) : ctw == 720 ? AN_K(SPX_TF_SMALL, 720)
+         : ctw == 661 ? AN_K(SPX_TF_SMALL, 661) : ctw == 120 ? AN_K(SPX_TF_SMALL, 120) : AN_K(SPX_TF_SMALL, 0);
+  return ctw == 240 ? AN_K(SPX_TF, 240) : ctw == 330 ? AN_K(SPX_TF, 330) : ctw == 120 ? AN_K(SPX_TF, 120) : ctw == 360 ? AN_K(SPX_TF, 360)
+       : ctw == 180 ? AN_K(SPX_TF, 180) : ctw == 480 ? AN_K(SPX_TF, 480) : AN_K(SPX_TF, 0);
+#undef AN_K
+}
+int spx_analysis_vgprs(const SpxPlanDev& P, int* scratch_bytes) {
+  return spx_kernel_vgprs(spx_analysis_select(P.tile_frames, plan_ct_window(P)).fn, scratch_bytes);
+}
+
 void spx_launch_analysis(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, int n_tiles,
                          const int16_t* in, SpxFrameRec* rec, SpxTapsDev taps, const int* tile_order, int* tile_flags,
                          hipStream_t st) {
   if (n_tiles <= 0) return;
-  const size_t lds = spx_analysis_lds_bytes(P);
-  const int ctw = plan_ct_window(P);
-#define SPX_LAUNCH_ANALYSIS(TFV, WV)                                                                                   \
-  hipLaunchKernelGGL((spx_analysis_kernel<TFV, WV>), dim3(n_tiles), dim3(SPX_BLOCK), lds, st, P, streams, n_streams, in, \
-                     rec, taps, tile_order, tile_flags, (const float*)nullptr, 0)
-  if (P.tile_frames == SPX_TF_TINY) {
-    SPX_LAUNCH_ANALYSIS(SPX_TF_TINY, 0);
-  } else if (P.tile_frames == SPX_TF_SMALL) {
-    if (ctw == 240) SPX_LAUNCH_ANALYSIS(SPX_TF_SMALL, 240); else if (ctw == 330) SPX_LAUNCH_ANALYSIS(SPX_TF_SMALL, 330);
-    else if (ctw == 720) SPX_LAUNCH_ANALYSIS(SPX_TF_SMALL, 720); else if (ctw == 661) SPX_LAUNCH_ANALYSIS(SPX_TF_SMALL, 661);
-    else if (ctw == 120) SPX_LAUNCH_ANALYSIS(SPX_TF_SMALL, 120);
-    else SPX_LAUNCH_ANALYSIS(SPX_TF_SMALL, 0);
-  } else {
-    if (ctw == 240) SPX_LAUNCH_ANALYSIS(SPX_TF, 240); else if (ctw == 330) SPX_LAUNCH_ANALYSIS(SPX_TF, 330);
-    else if (ctw == 120) SPX_LAUNCH_ANALYSIS(SPX_TF, 120); else if (ctw == 360) SPX_LAUNCH_ANALYSIS(SPX_TF, 360);
-    else if (ctw == 180) SPX_LAUNCH_ANALYSIS(SPX_TF, 180);
-    else if (ctw == 480) SPX_LAUNCH_ANALYSIS(SPX_TF, 480);
-    else SPX_LAUNCH_ANALYSIS(SPX_TF, 0);
-  }
-#undef SPX_LAUNCH_ANALYSIS
-}
-
-int spx_analysis_vgprs(const SpxPlanDev& P, int* scratch_bytes) {
-  const int ctw = plan_ct_window(P);
-  const bool small = P.tile_frames == SPX_TF_SMALL;
-  const void* fn;
-#define SPX_AN_FN(TFV, WV) reinterpret_cast<const void*>(spx_analysis_kernel<TFV, WV>)
-  if (P.tile_frames == SPX_TF_TINY) fn = SPX_AN_FN(SPX_TF_TINY, 0);
-  else if (small) fn = ctw == 240 ? SPX_AN_FN(SPX_TF_SMALL, 240) : ctw == 330 ? SPX_AN_FN(SPX_TF_SMALL, 330)
-                     : ctw == 720 ? SPX_AN_FN(SPX_TF_SMALL, 720) : ctw == 661 ? SPX_AN_FN(SPX_TF_SMALL, 661)
-                     : ctw == 120 ? SPX_AN_FN(SPX_TF_SMALL, 120) : SPX_AN_FN(SPX_TF_SMALL, 0);
-  else fn = ctw == 240 ? SPX_AN_FN(SPX_TF, 240) : ctw == 330 ? SPX_AN_FN(SPX_TF, 330) : ctw == 120 ? SPX_AN_FN(SPX_TF, 120)
-          : ctw == 360 ? SPX_AN_FN(SPX_TF, 360) : ctw == 480 ? SPX_AN_FN(SPX_TF, 480) : ctw == 180 ? SPX_AN_FN(SPX_TF, 180)
-          : SPX_AN_FN(SPX_TF, 0);
-#undef SPX_AN_FN
-  return spx_kernel_vgprs(fn, scratch_bytes);
+  SpxLaunch<SpxAnalysisArgs>::go(spx_analysis_select(P.tile_frames, plan_ct_window(P)), n_tiles, spx_analysis_lds_bytes(P), st, P, streams,
+                                 n_streams, in, rec, taps, tile_order, tile_flags, nullptr, 0);
 }
 
 void spx_launch_analysis_frames(const SpxPlanDev& P, const SpxStreamDev* streams, int n_tiles, const float* frames,
@@ -1602,14 +1585,7 @@ void spx_launch_analysis_frames(const SpxPlanDev& P, const SpxStreamDev* streams
   if (n_tiles <= 0) return;
   SpxPlanDev Q = P;
   if (Q.tile_frames != SPX_TF_SMALL && Q.tile_frames != SPX_TF_TINY) Q.tile_frames = SPX_TF;   // (smaller tiles above about 49 / 61 kHz)
-  const size_t lds = analysis_lds_bytes(Q, false);  // the plan-driven instantiation
-  if (Q.tile_frames == SPX_TF_TINY)
-    hipLaunchKernelGGL((spx_analysis_kernel<SPX_TF_TINY, 0>), dim3(n_tiles), dim3(SPX_BLOCK), lds, st, Q, streams, 1,
-                       (const int16_t*)nullptr, rec, taps, (const int*)nullptr, (int*)nullptr, frames, preemph ? 1 : 2);
-  else if (Q.tile_frames == SPX_TF_SMALL)
-    hipLaunchKernelGGL((spx_analysis_kernel<SPX_TF_SMALL, 0>), dim3(n_tiles), dim3(SPX_BLOCK), lds, st, Q, streams, 1,
-                       (const int16_t*)nullptr, rec, taps, (const int*)nullptr, (int*)nullptr, frames, preemph ? 1 : 2);
-  else
-    hipLaunchKernelGGL((spx_analysis_kernel<SPX_TF, 0>), dim3(n_tiles), dim3(SPX_BLOCK), lds, st, Q, streams, 1,
-                       (const int16_t*)nullptr, rec, taps, (const int*)nullptr, (int*)nullptr, frames, preemph ? 1 : 2);
+  // the plan-driven instantiation
+  SpxLaunch<SpxAnalysisArgs>::go(spx_analysis_select(Q.tile_frames, 0), n_tiles, analysis_lds_bytes(Q, false), st, Q, streams, 1, nullptr, rec,
+                                 taps, nullptr, nullptr, frames, preemph ? 1 : 2);
 }

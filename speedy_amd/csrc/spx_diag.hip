@@ -17,20 +17,18 @@ const char* spx_batch_kernel_names_lean(spx_plan_t plan, int n_streams, int max_
 static const char* kernel_names(spx_plan_t plan, int n_streams, int max_channels, int speedup_only, bool lean) {
   static thread_local char buf[256];
   const SpxPlanDev& d = plan->dev;
-  const SpxWalkConfig c = spx_walk_config(d, n_streams, max_channels < 1 ? 1 : max_channels, speedup_only != 0, false, lean, speedup_only == 0);
-  char walk[96];
-  if (c.fast_kernel && c.slow)
-    snprintf(walk, sizeof(walk), "spx_walk_fast_kernel<%d, %d, 0, 0, %d>", c.nwm, c.nwc, max_channels > 1 ? 3 : 2);
-  else if (c.fast_kernel)
-    {
-      const bool ct_rate = d.rate == 16000 || d.rate == 22050;
-      const bool lng = ct_rate && c.nwm == 4 && c.nwc == 4 && c.wcap == 8192;   // spx_launch_walk_fast's long-window instantiations
-      snprintf(walk, sizeof(walk), "spx_walk_fast_kernel<%d, %d, %d, %d, %d>", c.nwm, c.nwc,
-               (ct_rate && (lng || c.wcap == ((c.nwc == 0 && c.nwm <= 2) ? 1536 : 4096))) ? d.rate : 0, lng ? 1 : 0, max_channels > 1 ? 1 : 0);
-    }
-  else
-    snprintf(walk, sizeof(walk), "spx_walk_kernel<%d, %d>", c.nw, c.mode);
-  snprintf(buf, sizeof(buf), "spx_analysis_kernel<%d, %d>;spx_tension_kernel;%s", d.tile_frames, spx_analysis_ct_window(d), walk);
+  // the selectors' picks, spelled as a profiler spells a template-id: nothing about the choice is decided here
+  const SpxWalkConfig c = spx_walk_config(d, {.n_streams = n_streams, .max_channels = max_channels, .speedup_only = speedup_only != 0,
+                                              .any_speed = speedup_only == 0, .lean = lean});
+  size_t at = 0;
+  auto put = [&](const SpxKernelChoice& k) {
+    at += snprintf(buf + at, sizeof(buf) - at, "%s<", k.name);
+    for (int i = 0; i < k.n_targs; i++) at += snprintf(buf + at, sizeof(buf) - at, i ? ", %d" : "%d", k.targs[i]);
+    at += snprintf(buf + at, sizeof(buf) - at, ">");
+  };
+  put(spx_analysis_select(d.tile_frames, spx_analysis_ct_window(d)));
+  at += snprintf(buf + at, sizeof(buf) - at, ";spx_tension_kernel;");
+  put(c.kernel);
   return buf;
 }
 
@@ -41,10 +39,10 @@ int spx_debug_kernel_vgprs(int which) {
   const SpxPlanDev* P = spx_internal_shared_plan(rate, 0);
   if (!P) return -1;
   switch (which) {
-    case 1: return spx_walk_vgprs(*P, 256, 1, true, false);
-    case 2: return spx_walk_vgprs(*P, 256, 1, true, true);
+    case 1: return spx_walk_vgprs(*P, {.n_streams = 256, .max_channels = 1, .speedup_only = true}, nullptr);
+    case 2: return spx_walk_vgprs(*P, {.n_streams = 256, .max_channels = 1, .speedup_only = true, .lean = true}, nullptr);
     case 3: case 4: return spx_analysis_vgprs(*P);
-    case 5: return spx_walk_vgprs(*P, 256, 2, true, false);
+    case 5: return spx_walk_vgprs(*P, {.n_streams = 256, .max_channels = 2, .speedup_only = true}, nullptr);
     default: return -1;
   }
 }
@@ -55,9 +53,10 @@ int spx_debug_kernel_vgprs(int which) {
 int spx_debug_walk_info(int sample_rate, int channels, int n_streams, int speedup_only, int short_jobs, int lean, int* out) {
   const SpxPlanDev* P = spx_internal_shared_plan(sample_rate, 0);
   if (!P || !out) return -1;
-  const SpxWalkConfig c = spx_walk_config(*P, n_streams, channels < 1 ? 1 : channels, speedup_only != 0, short_jobs != 0, lean != 0, speedup_only == 0);
+  const SpxWalkConfig c = spx_walk_config(*P, {.n_streams = n_streams, .max_channels = channels, .speedup_only = speedup_only != 0,
+                                               .any_speed = speedup_only == 0, .short_jobs = short_jobs != 0, .lean = lean != 0});
   int scratch = -1;
-  out[0] = spx_walk_kernel_regs(*P, n_streams, channels, speedup_only != 0, short_jobs != 0, lean != 0, &scratch, speedup_only == 0);
+  out[0] = spx_kernel_vgprs(c.kernel.fn, &scratch);
   out[1] = scratch;
   out[2] = (int)c.lds;
   out[3] = c.fast_kernel ? 16 * c.nwm + c.nwc : 0;

@@ -342,11 +342,11 @@ SpxSpeedClass speed_class(const spx_stream_job* jobs, int n) {
   if (c.speedup_only) c.any_speed = false;   // (the flag means: slow-down jobs are there)
   return c;
 }
-SpxModeWalk mode_walk(const SpxPlanDev& d, int n, int maxC, bool speedup_only, bool lean, bool any_speed, bool short_window) {
-  const SpxWalkConfig c = spx_walk_config(d, n, maxC, speedup_only, false, lean, any_speed, short_window);
+SpxModeWalk mode_walk(const SpxPlanDev& d, const SpxWalkAsk& ask) {
+  const SpxWalkConfig c = spx_walk_config(d, ask);
   SpxModeWalk w;
   w.lds = c.lds; w.waves = c.waves; w.fast_kernel = c.fast_kernel; w.nwc = c.nwc;
-  w.vgprs = spx_walk_vgprs(d, n, maxC, speedup_only, lean, any_speed, short_window);
+  w.vgprs = spx_kernel_vgprs(c.kernel.fn);
   return w;
 }
 // (cached per plan and shape: the register queries and spx_walk_config are not free, and the engine asks on every call)
@@ -360,10 +360,10 @@ static const SpxModeResources& mode_resources(spx_plan* plan, int n, int maxC, b
   memset(&R, 0, sizeof(R));
   R.cu_count = plan->cu_count;
   R.lds_per_cu = plan->lds_per_cu;
-  R.walk = mode_walk(d, n, maxC, speedup_only, false, any_speed, short_window);
+  R.walk = mode_walk(d, {.n_streams = n, .max_channels = maxC, .speedup_only = speedup_only, .any_speed = any_speed, .short_window = short_window});
   R.walk_lean = R.walk;
   if (maxC == 1 && n <= plan->cu_count && R.walk.fast_kernel && R.walk.nwc > 0) {
-    R.walk_lean = mode_walk(d, n, maxC, speedup_only, true, any_speed);
+    R.walk_lean = mode_walk(d, {.n_streams = n, .max_channels = maxC, .speedup_only = speedup_only, .any_speed = any_speed, .lean = true});
     R.lean_valid = true;
   }
   R.tension_lds = spx_tension_lds_bytes();
@@ -676,9 +676,10 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
         // AHEAD: the counts are all published by the time the kernel starts -- its one poll returns at once -- and its workgroups
         // count themselves in for the next call's gate.
         SpxTimed tm(timed, 1, stw);
-        spx_launch_walk(d, dj, n, maxC, in, out, opt.rate ? opt.rate->d_tsm_n : n_out, states, scratch, (concurrent || ahead) ? d_ready : nullptr,
-                        speedup_only, stw, false, (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, M.launch_lean, any_speed,
-                        short_window_res || (!force && M.walk2 && !M.launch_lean && maxC > 1));
+        const SpxWalkAsk ask = {.n_streams = n, .max_channels = maxC, .speedup_only = speedup_only, .any_speed = any_speed, .lean = M.launch_lean,
+                                .short_window = short_window_res || (!force && M.walk2 && !M.launch_lean && maxC > 1)};
+        spx_launch_walk(d, ask, dj, in, out, opt.rate ? opt.rate->d_tsm_n : n_out, states, scratch, (concurrent || ahead) ? d_ready : nullptr,
+                        (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, stw);
       }
       if (opt.rate && c == nch - 1) {   // the rate stage: TSM buffer -> the caller's out, final counts -> n_out
         SpxTimed tm(timed, 3, stw);

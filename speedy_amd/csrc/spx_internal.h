@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <stdlib.h>
+#include <type_traits>
 
 // The library reads the documented environment variables only (INTEGRATION.md "Environment"): SPX_NO_POOL, SPX_POOL_*,
 // SPX_SHARED_GPU, SPX_LOCK_DIR, SPX_DEBUG_MODE, SPX_DEBUG_TRIAL, SPX_KEEP_HW_QUEUES and GPU_MAX_HW_QUEUES.  Variants are
@@ -182,21 +183,61 @@ void spx_launch_analysis_frames(const SpxPlanDev& P, const SpxStreamDev* streams
 void spx_launch_tension(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, SpxStreamState* states,
                         const SpxFrameRec* rec, float* scratch, SpxTapsDev taps, const int* tile_flags, int* speed_ready,
                         hipStream_t st);
-// speedup_only: every job has speed > 1 and 0 <= nonlinear <= 1 (and a streamed job has never had another setting),
-// so the time-scale stage only ever sees speeds >= 1: selects the walk kernel specialised for that.
-// any_speed (round 5; the batch engine): the jobs do NOT all speed up, but every speed the time-scale stage can be given is a valid
-// one below SPX_FAST_MAX_SPEED -- the speed-up kernel's instantiations that also run libsonic's insertPitchPeriod serve the batch
-// (spx_walk_fast.hip, MC + 2) instead of the general kernel.
-void spx_launch_walk(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, int max_channels,
-                     const int16_t* in, int16_t* out, int64_t* n_out, SpxStreamState* states, const float* scratch,
-                     const int* speed_ready, bool speedup_only, hipStream_t st, bool short_jobs = false, size_t lds_min = 0,
-                     bool lean = false, bool any_speed = false, bool short_window = false);
+// An instantiation of a kernel template as its family's selector picked it (spx_analysis_select, spx_walk_select,
+// spx_walk_fast_select -- each the ONE place its template-ids are written): the launch, the register query and the kernel's
+// name (spx_batch_kernel_names) all come from the same pick.
+struct SpxKernelChoice {
+  const char* name;  // the template's name, as a profiler prints it in front of the template values
+  const void* fn;    // host function pointer: hipLaunchKernel, spx_kernel_vgprs
+  int block;       // threads per workgroup
+  int n_targs;     // template values in use ...
+  int targs[5];    // ... in the template's order
+};
+// The argument lists of the three kernel templates (every instantiation of a template has its template's one signature): each
+// selector asserts its list against its kernel, and a launch through SpxLaunch<list> is type-checked against the list -- a
+// parameter added to a kernel stops the build at the selector, and then at every launch, as a direct launch would.
+using SpxAnalysisArgs = void(SpxPlanDev, const SpxStreamDev*, int, const int16_t*, SpxFrameRec*, SpxTapsDev, const int*, int*, const float*, int);
+using SpxWalkArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, int, const int*);
+using SpxWalkFastArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, const int*, int);
+template <typename F> struct SpxLaunch;
+template <typename... P> struct SpxLaunch<void(P...)> {
+  static void go(const SpxKernelChoice& k, int grid, size_t lds, hipStream_t st, P... p) {
+    void* args[] = {&p...};
+    // (a launch error surfaces at the callers' hipGetLastError or at their synchronisation, as with a direct launch)
+    (void)hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), args, lds, st);
+  }
+};
+// What a caller asks of the walk stage: the batch's shape and the flags that pick the kernel's form.  Call sites name the
+// fields they set.
+struct SpxWalkAsk {
+  int n_streams = 0;
+  int max_channels = 1;
+  // every job has speed > 1 and 0 <= nonlinear <= 1 (and a streamed job has never had another setting), so the time-scale
+  // stage only ever sees speeds >= 1: selects the walk kernel specialised for that
+  bool speedup_only = false;
+  // (round 5; the batch engine) the jobs do NOT all speed up, but every speed the time-scale stage can be given is a valid one
+  // below SPX_FAST_MAX_SPEED -- the speed-up kernel's instantiations that also run libsonic's insertPitchPeriod serve the batch
+  // (spx_walk_fast.hip, MC + 2) instead of the general kernel
+  bool any_speed = false;
+  // the streams bring a few pitch steps each (coalesced sonic2.h writes): latency form whatever their number
+  bool short_jobs = false;
+  // no output waves (and the usual window) although the streams have a CU each -- the search waves do the output work: one walk
+  // wave per SIMD instead of two, which is what lets two analysis waves of 168 registers sit beside it (22.05 kHz)
+  bool lean = false;
+  // the 4 + 4 form with the usual 4096-frame window where it would take the long one (36.9 instead of 69.7 KB of LDS per stream:
+  // two calls' walk workgroups AND an analysis workgroup on a CU -- a mixed call whose walk kernels overlap the previous call's)
+  bool short_window = false;
+};
+// lds_min: the caller wants the workgroups ONE to a CU (it asks for more than half a CU's LDS, spx_engine.hip); 0 otherwise
+void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStreamDev* streams, const int16_t* in, int16_t* out,
+                     int64_t* n_out, SpxStreamState* states, const float* scratch, const int* speed_ready, size_t lds_min,
+                     hipStream_t st);
 size_t spx_analysis_lds_bytes(const SpxPlanDev& P);
 int spx_analysis_ct_window(const SpxPlanDev& P);
 // The DFT of the spec run on the host (same operation order as the kernel): used to build the Rader tables.
 void spx_host_dft(int n, const int* radix, int nstages, const double* tw, const double* in, double* out);
 size_t spx_walk_lds_bytes(const SpxPlanDev& P, int max_channels, bool speedup_only);
-// What spx_launch_walk will do for a batch (kernel variant, waves and LDS per stream).
+// What spx_launch_walk will do for a batch (kernel instantiation, waves and LDS per stream).
 struct SpxWalkConfig {
   int mode;          // 0 general, 1 mono speed-up, 2 multi-channel speed-up
   bool fast_kernel;  // mode 1 on spx_walk_fast_kernel
@@ -205,21 +246,15 @@ struct SpxWalkConfig {
   int waves;         // waves per stream of the kernel that will run
   size_t lds;        // its LDS bytes per stream
   bool slow;         // the fast kernel's instantiation that also serves speeds below 1
+  SpxKernelChoice kernel;  // the instantiation itself
 };
-// short_jobs: the streams bring a few pitch steps each (coalesced sonic2.h writes): latency form whatever their number
-// lean: no output waves (and the usual window) although the streams have a CU each -- the search waves do the output work:
-// one walk wave per SIMD instead of two, which is what lets two analysis waves of 168 registers sit beside it (22.05 kHz)
-// short_window: the 4 + 4 form with the usual 4096-frame window where it would take the long one (36.9 instead of 69.7 KB of LDS per
-// stream: two calls' walk workgroups AND an analysis workgroup on a CU -- a mixed call whose walk kernels overlap the previous call's)
-SpxWalkConfig spx_walk_config(const SpxPlanDev& P, int n_streams, int max_channels, bool speedup_only, bool short_jobs = false,
-                              bool lean = false, bool any_speed = false, bool short_window = false);
+SpxWalkConfig spx_walk_config(const SpxPlanDev& P, const SpxWalkAsk& ask);
+SpxKernelChoice spx_walk_select(int nw, int mode);   // spx_walk.hip: the general kernel, waves per stream and mode
 // spx_walk_fast.hip
 size_t spx_walk_fast_lds_bytes(const SpxPlanDev& P, int wcap);
 bool spx_walk_fast_supports(const SpxPlanDev& P, int nwm);
-void spx_launch_walk_fast(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, const int16_t* in,
-                          int16_t* out, int64_t* n_out, SpxStreamState* states, const float* scratch,
-                          const int* speed_ready, int nwm, int nwc, int wcap, int max_channels, hipStream_t st, size_t lds_min = 0,
-                          bool slow = false);
+SpxKernelChoice spx_walk_fast_select(const SpxPlanDev& P, int nwm, int nwc, int wcap, int max_channels, bool slow);
+SpxKernelChoice spx_analysis_select(int tile_frames, int ct_window);   // spx_analysis.hip; ct_window 0: the plan-driven instantiation
 // n_out value of a stream whose producer kernel never delivered (concurrent mode poll limit): not an overflow
 #define SPX_NOUT_LOST_PRODUCER INT64_MIN
 size_t spx_tension_lds_bytes();
@@ -229,10 +264,7 @@ size_t spx_tension_lds_bytes();
 int spx_kernel_vgprs(const void* fn, int* scratch_bytes = nullptr);   // spx_engine.hip (one cache, behind a mutex)
 int spx_tension_vgprs();
 int spx_analysis_vgprs(const SpxPlanDev& P, int* scratch_bytes = nullptr);
-int spx_walk_vgprs(const SpxPlanDev& P, int n_streams, int max_channels, bool speedup_only, bool lean = false, bool any_speed = false,
-                   bool short_window = false);
-int spx_walk_kernel_regs(const SpxPlanDev& P, int n_streams, int max_channels, bool speedup_only, bool short_jobs, bool lean,
-                         int* scratch_bytes, bool any_speed = false, bool short_window = false);
+int spx_walk_vgprs(const SpxPlanDev& P, const SpxWalkAsk& ask, int* scratch_bytes);
 // speedyComputeSpeedFromTension (speedy.c:768-788) on the stream's state record: *speed_out = requested speed, the
 // duration sums of the record advance.
 void spx_launch_speed_from_tension(SpxStreamState* state, float tension, float Rg, float feedback, float* speed_out,

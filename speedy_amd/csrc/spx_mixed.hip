@@ -100,7 +100,7 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     for (const auto& j : gj[g]) any_nl = any_nl || j.nonlinear != 0.0f;
     SpxModeGroup mg;
     mg.n = (int)gj[g].size();
-    mg.walk = mode_walk(d, mg.n, maxC, SC.speedup_only, false, SC.any_speed);
+    mg.walk = mode_walk(d, {.n_streams = mg.n, .max_channels = maxC, .speedup_only = SC.speedup_only, .any_speed = SC.any_speed});
     if (mg.walk.lds > 160 * 1024) return fail(-1, "spx_batch_run_mixed: too many channels for the walk kernel's LDS window");
     mg.any_nonlinear = any_nl;
     mg.an_lds = spx_analysis_lds_bytes(d);

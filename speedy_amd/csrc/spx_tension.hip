@@ -36,7 +36,6 @@ __device__ __forceinline__ float iir_wave(const float* sA, float* sB, int n, flo
   for (int b0 = 0; b0 < n; b0 += 64) {
     const int m = n - b0 < 64 ? n - b0 : 64;
     const float ax = a * ((lane < m) ? sA[b0 + lane] : 0.0f);
-#ifndef SPX_TENSION_OLD_CHAIN
     if (m == 64) {
       // A full block: the chain runs on lane 0 alone -- per element one v_readlane (it ignores EXEC), the two dependent
       // operations and one LDS store at a constant offset; no per-element bound check, no lane masks.  (Before: ten
@@ -52,8 +51,6 @@ __device__ __forceinline__ float iir_wave(const float* sA, float* sB, int n, flo
       y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, y)));
       continue;
     }
-#endif
-#ifndef SPX_TENSION_OLD_CHAIN
     // a partial block (the last one; every block of a concurrent-mode chunk or of a streamed write): the same on lane 0,
     // with the bound check per element
     if (lane == 0) {
@@ -67,18 +64,6 @@ __device__ __forceinline__ float iir_wave(const float* sA, float* sB, int n, flo
       }
     }
     y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, y)));
-#else
-    float out = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 64; j++) {
-      if (j < m) {  // uniform
-        const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ax), j));
-        y = s + b * y;
-        out = (lane == j) ? y : out;
-      }
-    }
-    if (lane < m) sB[b0 + lane] = out;
-#endif
   }
   return y;
 }

@@ -901,13 +901,13 @@ static int walk_mode(const SpxPlanDev& P, int maxC, bool speedup_only) {
   return 0;
 }
 
-// Kernel variant, waves per stream and LDS per stream for a batch: the one place the launcher and the engine's
-// co-residency arithmetic both ask.
-SpxWalkConfig spx_walk_config(const SpxPlanDev& P, int n_streams, int maxC, bool speedup_only, bool short_jobs, bool lean, bool any_speed,
-                              bool short_window) {
-  if (maxC < 1) maxC = 1;
+// Kernel variant, waves per stream and LDS per stream for a batch, and the instantiation itself (the two selectors' pick): the one
+// place the launcher, the register query, the kernel names and the engine's co-residency arithmetic all ask.
+SpxWalkConfig spx_walk_config(const SpxPlanDev& P, const SpxWalkAsk& ask) {
+  const int n_streams = ask.n_streams, maxC = ask.max_channels < 1 ? 1 : ask.max_channels;
+  const bool speedup_only = ask.speedup_only, short_jobs = ask.short_jobs, lean = ask.lean, short_window = ask.short_window;
   SpxWalkConfig c;
-  const bool slow = !speedup_only && any_speed;
+  const bool slow = !speedup_only && ask.any_speed;
   c.mode = walk_mode(P, maxC, speedup_only || slow);
   c.fast_kernel = c.mode == 1 || c.mode == 2;  // spx_walk_fast_kernel: mono and (round 2) multi-channel
   // Waves per stream of spx_walk_kernel.  Measured on MI355X, 10 s streams (ms per call; 2 / 4 / 8 waves): 256 streams
@@ -972,64 +972,41 @@ SpxWalkConfig spx_walk_config(const SpxPlanDev& P, int n_streams, int maxC, bool
     c.waves = c.nw;
     c.lds = (size_t)walk_lds_layout(P, maxC, c.mode).total;
   }
+  c.kernel = c.fast_kernel ? spx_walk_fast_select(P, c.nwm, c.nwc, c.wcap, maxC, c.slow) : spx_walk_select(c.nw, c.mode);
   return c;
 }
-int spx_walk_fast_vgprs(const SpxPlanDev& P, int nwm, int nwc, int wcap, int maxC, int* scratch_bytes = nullptr, bool slow = false);
-int spx_walk_kernel_regs(const SpxPlanDev& P, int n_streams, int maxC, bool speedup_only, bool short_jobs, bool lean, int* scratch_bytes,
-                         bool any_speed, bool short_window) {
-  const SpxWalkConfig cfg = spx_walk_config(P, n_streams, maxC < 1 ? 1 : maxC, speedup_only, short_jobs, lean, any_speed, short_window);
-  if (cfg.fast_kernel) return spx_walk_fast_vgprs(P, cfg.nwm, cfg.nwc, cfg.wcap, maxC, scratch_bytes, cfg.slow);
-  const void* fn;
-#define SPX_FN_W(NWV) (cfg.mode == 1 ? reinterpret_cast<const void*>(spx_walk_kernel<NWV, 1>)   \
-                       : cfg.mode == 2 ? reinterpret_cast<const void*>(spx_walk_kernel<NWV, 2>) \
-                                       : reinterpret_cast<const void*>(spx_walk_kernel<NWV, 0>))
-  if (cfg.nw == 8) fn = SPX_FN_W(8);
-  else fn = SPX_FN_W(4);
-#undef SPX_FN_W
-  return spx_kernel_vgprs(fn, scratch_bytes);
+// The one place that maps (waves per stream, mode) to an instantiation of the general kernel.
+SpxKernelChoice spx_walk_select(int nw, int mode) {
+#define WALK_K(NWV, FASTV) SpxKernelChoice{"spx_walk_kernel", reinterpret_cast<const void*>(spx_walk_kernel<NWV, FASTV>), 64 * NWV, 2, {NWV, FASTV}}
+  static_assert(std::is_same<decltype(spx_walk_kernel<8, 1>), SpxWalkArgs>::value, "SpxWalkArgs is the kernel's argument list");
+  if (nw == 8) return mode == 1 ? WALK_K(8, 1) : mode == 2 ? WALK_K(8, 2) : WALK_K(8, 0);
+  return mode == 1 ? WALK_K(4, 1) : mode == 2 ? WALK_K(4, 2) : WALK_K(4, 0);
+#undef WALK_K
 }
-int spx_walk_vgprs(const SpxPlanDev& P, int n_streams, int maxC, bool speedup_only, bool lean, bool any_speed, bool short_window) {
-  return spx_walk_kernel_regs(P, n_streams, maxC, speedup_only, false, lean, nullptr, any_speed, short_window);
+int spx_walk_vgprs(const SpxPlanDev& P, const SpxWalkAsk& ask, int* scratch_bytes) {
+  return spx_kernel_vgprs(spx_walk_config(P, ask).kernel.fn, scratch_bytes);
 }
 size_t spx_walk_lds_bytes(const SpxPlanDev& P, int maxC, bool speedup_only) {
-  return spx_walk_config(P, 256, maxC, speedup_only).lds;
+  return spx_walk_config(P, {.n_streams = 256, .max_channels = maxC, .speedup_only = speedup_only}).lds;
 }
 
 static std::atomic<int> g_last_walk_form{0};
 extern "C" int spx_debug_last_walk_form(void) { return g_last_walk_form.load(std::memory_order_relaxed); }
 
-void spx_launch_walk(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, int maxC, const int16_t* in,
-                     int16_t* out, int64_t* n_out, SpxStreamState* states, const float* scratch,
-                     const int* speed_ready, bool speedup_only, hipStream_t st, bool short_jobs, size_t lds_min, bool lean, bool any_speed,
-                     bool short_window) {
+void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStreamDev* streams, const int16_t* in, int16_t* out,
+                     int64_t* n_out, SpxStreamState* states, const float* scratch, const int* speed_ready, size_t lds_min,
+                     hipStream_t st) {
+  const int n_streams = ask.n_streams;
   if (n_streams <= 0) return;
-  if (maxC < 1) maxC = 1;
-  const SpxWalkConfig cfg = spx_walk_config(P, n_streams, maxC, speedup_only, short_jobs, lean, any_speed, short_window);
+  const int maxC = ask.max_channels < 1 ? 1 : ask.max_channels;
+  const SpxWalkConfig cfg = spx_walk_config(P, ask);
   g_last_walk_form.store(cfg.fast_kernel ? 16 * cfg.nwm + cfg.nwc : 0, std::memory_order_relaxed);
   static const bool dbg_mode = getenv("SPX_DEBUG_MODE") != nullptr;
   if (dbg_mode) fprintf(stderr, "[spx walk] rate %d n %d maxC %d: %s %d + %d waves, window %d frames, %zu B LDS per stream (at least %zu asked)\n", P.rate, n_streams, maxC,
                         cfg.fast_kernel ? "fast kernel" : "general kernel", cfg.fast_kernel ? cfg.nwm : cfg.nw, cfg.fast_kernel ? cfg.nwc : 0, cfg.wcap, cfg.lds, lds_min);
-  if (cfg.fast_kernel) {
-    spx_launch_walk_fast(P, streams, n_streams, in, out, n_out, states, scratch, speed_ready, cfg.nwm, cfg.nwc, cfg.wcap,
-                         maxC, st, lds_min, cfg.slow);
-    return;
-  }
-  const int fast = cfg.mode;
-  const int nw = cfg.nw;
-  const WalkLds LY = walk_lds_layout(P, maxC, fast);
-#define SPX_LAUNCH_WALK(NWV)                                                                                     \
-  do {                                                                                                           \
-    if (fast == 1)                                                                                               \
-      hipLaunchKernelGGL((spx_walk_kernel<NWV, 1>), dim3(n_streams), dim3(64 * NWV), LY.total, st, P, streams,   \
-                         in, out, n_out, states, scratch, maxC, speed_ready);                                    \
-    else if (fast == 2)                                                                                          \
-      hipLaunchKernelGGL((spx_walk_kernel<NWV, 2>), dim3(n_streams), dim3(64 * NWV), LY.total, st, P, streams,   \
-                         in, out, n_out, states, scratch, maxC, speed_ready);                                    \
-    else                                                                                                         \
-      hipLaunchKernelGGL((spx_walk_kernel<NWV, 0>), dim3(n_streams), dim3(64 * NWV), LY.total, st, P, streams,   \
-                         in, out, n_out, states, scratch, maxC, speed_ready);                                    \
-  } while (0)
-  if (nw == 8) SPX_LAUNCH_WALK(8);
-  else SPX_LAUNCH_WALK(4);
-#undef SPX_LAUNCH_WALK
+  // lds_min (the fast kernel's callers): walk kernels of several groups launched side by side otherwise land two to a CU here and
+  // there, and those chains end the call (spx_engine.hip)
+  const size_t lds = cfg.fast_kernel && lds_min > cfg.lds ? lds_min : cfg.lds;
+  if (cfg.fast_kernel) SpxLaunch<SpxWalkFastArgs>::go(cfg.kernel, n_streams, lds, st, P, streams, in, out, n_out, states, scratch, speed_ready, cfg.wcap);
+  else SpxLaunch<SpxWalkArgs>::go(cfg.kernel, n_streams, lds, st, P, streams, in, out, n_out, states, scratch, maxC, speed_ready);
 }

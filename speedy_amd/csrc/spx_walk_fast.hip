@@ -52,17 +52,9 @@
 #define SPX_PAD_MONO 48  // 16 kHz: the refine rectangle's reads become conflict-free (tools/lds_conflict_model.py: 267 -> 202 LDS cycles per step)
 #endif
 // Branch hints for the step loop: the compiler lays the expected side out as the fall-through (a taken branch costs a wave
-// ~20 cycles, tools/ubench/issue_costs.hip).  -DSPX_NO_HINTS builds the loop as the compiler would place it by itself.
-#ifdef SPX_NO_HINTS
-#define SPX_LIKELY(x) (x)
-#define SPX_UNLIKELY(x) (x)
-#else
+// ~20 cycles, tools/ubench/issue_costs.hip).
 #define SPX_LIKELY(x) __builtin_expect(!!(x), 1)
 #define SPX_UNLIKELY(x) __builtin_expect(!!(x), 0)
-#endif
-#ifndef SPX_PAD_PL
-#define SPX_PAD_PL 0
-#endif
 #ifndef SPX_CT_WCAP
 #define SPX_CT_WCAP 4096  // window frames of the rate-specialised kernels
 #endif
@@ -74,15 +66,6 @@
 #endif
 #define SPX_CT_WCAP_OF(NWMV, NWCV) (((NWCV) == 0 && (NWMV) <= 2) ? SPX_CT_WCAP_TP : SPX_CT_WCAP)
 enum { FCMD_STEP = 1, FCMD_COPY = 2, FCMD_REFILL = 3, FCMD_POLL = 4, FCMD_EXIT = 5 };
-// Diagnostic builds only (-DSPX_PROBE_SITE=k through tools/build_variant.sh + tools/variant_times.sh; rounds 4-5: tools/slack_probe.sh, in the history): about 100 cycles of s_nop at ONE place of the step.  What
-// the walk kernel's time grows by tells whether that place is on the chain (all of it shows) or in the shadow of a wait (none
-// does) -- in-kernel time stamps cannot tell since the waits went: reading s_memtime drains the LDS counter and serialises
-// exactly the overlap that is to be measured.  Never in the product.
-#ifdef SPX_PROBE_SITE
-#define SPX_PROBE(k) do { if ((k) == SPX_PROBE_SITE) asm volatile(".rept 7\n\ts_nop 15\n\t.endr" ::: "memory"); } while (0)
-#else
-#define SPX_PROBE(k)
-#endif
 #define FCMD_INTS 64  // ints per command slot: field k is written by lane k of the publishing wave
 // at most this many coarse groups / ragged refine tasks per lane (22.05 kHz: 303 groups and 441 tasks over the search lanes):
 // constants of the instantiation -- fewer search waves, more tasks per lane
@@ -149,7 +132,7 @@ static __host__ __device__ inline FastLds fast_lds_layout_i(int minPeriod, int m
   const int plStride = ((wcap / skip + 4) + 1) & ~1;  // elements per plane (even)
   L.plStrideB = plStride * 2;
   const int plb = (plStride * skip * 2 + 15) & ~15;
-  L.off_pl = o; o += plb + SPX_PAD_PL;
+  L.off_pl = o; o += plb;
   L.off_plB = o; o += plb;
   L.off_sumW = o;
   if (skip >= 6 || fast_wide_coarse(minPeriod, maxPeriod, skip)) o += 512 * 4;   // (the rates the eight-search-wave form serves, or the wide coarse select) behind everything else: no other offset moves
@@ -384,7 +367,6 @@ __device__ __forceinline__ void fast_refill_onepass(const FastOut& X, const Fast
 template <int NT, bool MC>
 __device__ __forceinline__ void fast_refill(const FastOut& X, const FastLds& LY, int skip, pos_t nb, pos_t limit) {
   fast_sync();  // everyone is done reading the old window
-#ifndef SPX_NO_FAST_REFILL
   {
     const int C = MC ? X.C : 1;
     if (C <= 2 && (skip == 4 || skip == 5) && limit - nb >= LY.wcap + 4 * skip && ((size_t)(X.in + (size_t)nb * C) & 3) == 0) {
@@ -393,7 +375,6 @@ __device__ __forceinline__ void fast_refill(const FastOut& X, const FastLds& LY,
       return;
     }
   }
-#endif
   const int wcap = LY.wcap;
   const int C = MC ? X.C : 1;
   unsigned short* monoH = reinterpret_cast<unsigned short*>(X.lds + LY.off_mono);
@@ -610,17 +591,8 @@ __device__ __forceinline__ int fast_writelane_impl(int v, int old, T) { return o
 // A masked pair of a SAD: both operands ANDed with the mask.  (Round 5 tried ONE v_bfi_b32 in front of the v_sad_u16 instead -- the
 // halves the mask switches off read `a` on both sides, four instructions fewer per coarse group and one per ragged task: bit-equal
 // and 0.2 - 1 % SLOWER in both launch orders, profiles/r05/r5u_bfi_ab.txt: the VOP3 encoding is eight bytes where v_and is four, and
-// the step loop's speed follows its fetch lines more than its instruction count.  -DSPX_SAD_BFI builds it.)
-#ifdef SPX_SAD_BFI
-__device__ __forceinline__ unsigned sad_masked_b(unsigned m, unsigned b, unsigned a) {
-  unsigned r;
-  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "v"(b), "v"(a));
-  return r;
-}
-#define SPX_SAD_MASKED(M, A, B, ACC) __builtin_amdgcn_sad_u16((A), sad_masked_b((M), (B), (A)), (ACC))
-#else
+// the step loop's speed follows its fetch lines more than its instruction count.)
 #define SPX_SAD_MASKED(M, A, B, ACC) __builtin_amdgcn_sad_u16((A) & (M), (B) & (M), (ACC))
-#endif
 
 // byte address of the aligned dword holding elements (e, e+1) of a u16 array kept twice, the second copy shifted by one
 // element: base + 2e for even e, (base of the shifted copy - 2) + 2e for odd e;  d2 = shiftedBase - 2 - base
@@ -849,7 +821,6 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
       rb[k] = *reinterpret_cast<const unsigned*>(lds + pair_addr(LY.off_mono, dA, ea + lo + rt[k]));
     }
     FSTAMP(12);
-    SPX_PROBE(6);   // behind the ragged loads, in front of the rectangle set-up
     // common share: the c0 pairs every lag of the search has form a rectangle of lags x pairs, cut into groups of four
     // pairs and dealt to ALL search lanes: lane = (lag myT, chunk myC) takes NGL = (c0 / 4) / NCH consecutive groups --
     // the same count for every lane, so no masks -- plus, for the first chunks, one of the left-over groups and one of
@@ -932,10 +903,8 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
         const int cp_n = uni(c[5]), cp_src = uni(c[6]), cp_out = uni(c[7]);
         const pos_t nb = uni(c[9]);
         if (type != FCMD_STEP) lim = uni(c[8]);  // a step command carries fields 0..4 only
-#ifndef SPX_EXP_NO_OUTPUT   // (diagnostic builds: the output waves only take part in the barriers -- WRONG audio, same chain)
         fast_outputs<64 * NWC, MCH>(X, t0o, xf_n, xf_down, xf_period, xf_out, type == FCMD_STEP ? 0 : cp_n, cp_src,
                                cp_out, lim, wb);
-#endif
         if (type == FCMD_STEP) {
           nsteps++;
           fast_sync();            // the step's second barrier (refine sums complete)
@@ -1054,12 +1023,8 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
   // exactly one workgroup barrier before the next command is published, and the two slots alternate, so a slot is
   // rewritten only after the output waves have consumed it.  Field k of a command is written by lane k of the last
   // search wave (v_writelane: no EXEC juggling).  NWC == 0: the search waves do the output work themselves.
-#ifdef SPX_EXP_NO_OUTPUT_LEAN   // (diagnostic builds: the forms without output waves produce NO audio -- the chain's length without its output work)
-#define SPX_LEAN_OUTPUTS(CP_N, CP_SRC, CP_OUT) do { } while (0)
-#else
 #define SPX_LEAN_OUTPUTS(CP_N, CP_SRC, CP_OUT) \
   fast_outputs<64 * NWM, MCH>(X, tid, xf_n, xf_down, xf_period, xf_out, (int)(CP_N), (pos_t)(CP_SRC), (pos_t)(CP_OUT), limit, wbase)
-#endif
 #define FAST_PUBLISH(TYPE, CP_N, CP_SRC, CP_OUT, NB)                                                                   \
   do {                                                                                                                 \
     if constexpr (NWC > 0) {                                                                                           \
@@ -1131,13 +1096,11 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
     }
     FSTAMP(2);
     const int o = (int)(pos - wbase);
-    SPX_PROBE(1);   // in front of the coarse operand addresses
     // ---- coarse search on the decimated signal: each lane its constant group(s) of pair slots ----
     int bestC;
     {
       unsigned a[FCG][4], b[FCG][4];
       coarse_loads(o, a, b);
-      SPX_PROBE(2);   // behind the coarse loads (their shadow)
       FAST_PUBLISH(FCMD_STEP, 0, 0, 0, 0);  // the previous step's cross-fade rides on this step's command; behind the loads
 #pragma unroll
       for (int g = 0; g < FCG; g++) {
@@ -1149,10 +1112,8 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
         }
       }
       FSTAMP(3);
-      SPX_PROBE(3);   // behind the coarse atomics, in front of the first barrier
       fast_sync();
       FSTAMP(4);
-      SPX_PROBE(4);   // behind the first barrier, in front of the coarse select
       if (wave == 0) {                                 // the buffer the previous step used: everyone is past it
         sumC[(1 - tg) * CS + lane] = 0;
         if constexpr (WIDEC) sumC[(1 - tg) * CS + 64 + lane] = 0;
@@ -1163,7 +1124,6 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
       else bestC = fast_select(dsum, scaleC, validC, false, minC, kmin);
     }
     FSTAMP(5);
-    SPX_PROBE(5);   // behind the coarse select, in front of the refine set-up
     // ---- refine at full rate around the coarse winner ----
     int period = (minC + bestC) * skip;
     int lo = period - (skip << 2), hi = period + (skip << 2);
@@ -1184,11 +1144,6 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
       {
         const int pc = (!WIDE && lane == 63) ? prevPeriod : p;
         const float fp = (float)pc;
-#ifdef SPX_IEEE_DIV
-        (void)rinv;
-        nLane = ge2 ? (int)(fp / sm1) : pc;
-        remLane = ge2 ? 0 : (int)(fp * twom / sm1);
-#else
         if constexpr (ANYK) {
           const int q = (int)((kind == 0 ? fp : fp * twom) / sm1);
           nLane = (kind & 1) ? pc : q;
@@ -1197,14 +1152,9 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
           nLane = ge2 ? (int)fast_div(fp, sm1, rinv) : pc;
           remLane = ge2 ? 0 : (int)fast_div(fp * twom, sm1, rinv);
         }
-#endif
         if constexpr (WIDE) {
           const int pc2 = (lane == 63) ? prevPeriod : p2;
           const float fp2 = (float)pc2;
-#ifdef SPX_IEEE_DIV
-          nLane2 = ge2 ? (int)(fp2 / sm1) : pc2;
-          remLane2 = ge2 ? 0 : (int)(fp2 * twom / sm1);
-#else
           if constexpr (ANYK) {
             const int q2 = (int)((kind == 0 ? fp2 : fp2 * twom) / sm1);
             nLane2 = (kind & 1) ? pc2 : q2;
@@ -1213,16 +1163,13 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
             nLane2 = ge2 ? (int)fast_div(fp2, sm1, rinv) : pc2;
             remLane2 = ge2 ? 0 : (int)fast_div(fp2 * twom, sm1, rinv);
           }
-#endif
         }
       }
       asm volatile("" ::"v"(nLane), "v"(remLane));  // here, while the sums are on their way -- not behind the barrier
       if constexpr (WIDE) asm volatile("" ::"v"(nLane2), "v"(remLane2));
       FSTAMP(6);
-      SPX_PROBE(7);   // behind the refine atomics and the candidate divisions, in front of the second barrier
       fast_sync();  // the step's one workgroup barrier: refine sums complete, the output waves done with the command
       FSTAMP(7);
-      SPX_PROBE(8);   // behind the second barrier, in front of the refine select
       if (wave == 0) {
         sumR[(1 - tg) * RS + lane] = 0;
         if constexpr (WIDE) sumR[(1 - tg) * RS + 64 + lane] = 0;
@@ -1238,7 +1185,6 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
     period = lo + best;
     const int minDiff = (int)(kmin >> 16);  // floor(diff / lag) of the winner
     FSTAMP(8);
-    SPX_PROBE(9);   // behind the refine select (decision, bookkeeping)
     // Previous-period rule (libsonic prevPeriodBetter, preferNewPeriod = 1).  Only "maxDiff > 3*minDiff" is ever asked
     // of the worst lag, and max_p floor(d_p/p) = floor(max_p d_p/p), so the test is "some lag has d_p >= (3*minDiff+1)*p".
     int ret = period, sel = best;
@@ -1432,7 +1378,6 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
             i = e;
             const pos_t availE = (linear && !flushBlk) ? n_tsm : availBlk + (i + 1) * perEvent;
             FSTAMP(0);
-            SPX_PROBE(10);  // once per EVENT of the hot loop (not per step)
             const float sm1 = speed - 1.0f;
             const float rinv = fast_rcp_refined(sm1);
             pos_t pos = base;
@@ -1455,7 +1400,6 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
         // ... and the same for a stream that runs at 1 < speed < 2: steps with ge2 = false a constant, each followed by the pass
         // that copies what it left to copy; events at speed >= 2 or unity leave for the general code (16 kHz mono 1.5x: walk
         // 1.50 -> 1.46 ms per 256 x 10 s, 22.05 kHz stereo 1.5x 1.25 -> 1.18; profiles/r03/r03at_hot_lt2.txt)
-#ifndef SPX_NO_HOT_LT2
         else {
           for (;;) {
             const unsigned long long runnable = __builtin_amdgcn_ballot_w64(
@@ -1495,7 +1439,6 @@ spx_walk_fast_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, con
             i++;
           }
         }
-#endif
         // the general code: one event
         if (i >= nIn) break;
         const unsigned long long runnable = __builtin_amdgcn_ballot_w64(
@@ -1577,103 +1520,42 @@ bool spx_walk_fast_supports(const SpxPlanDev& P, int nwm) {
   return total <= fcg_of(nwm) * 64 * nwm && ragged <= frg_of(nwm) * 64 * nwm;
 }
 
-// numRegs of the instantiation spx_launch_walk_fast picks for (nwm, nwc) at this plan's rate
-int spx_walk_fast_vgprs(const SpxPlanDev& P, int nwm, int nwc, int wcap, int maxC, int* scratch_bytes, bool slow) {
-  const void* fn = nullptr;
-  if (fast_wide_coarse(P.minPeriod, P.maxPeriod, P.skip)) {   // the wide-coarse instantiations (SPEC = 2): plan-driven, 4 + 4 or 4 + 0 waves
-#define SPX_FN_WC(C) (slow ? (maxC > 1 ? reinterpret_cast<const void*>(spx_walk_fast_kernel<4, C, 0, 2, 3>) : reinterpret_cast<const void*>(spx_walk_fast_kernel<4, C, 0, 2, 2>)) \
-                           : (maxC > 1 ? reinterpret_cast<const void*>(spx_walk_fast_kernel<4, C, 0, 2, 1>) : reinterpret_cast<const void*>(spx_walk_fast_kernel<4, C, 0, 2, 0>)))
-    fn = nwc >= 4 ? SPX_FN_WC(4) : SPX_FN_WC(0);
-#undef SPX_FN_WC
-    return spx_kernel_vgprs(fn, scratch_bytes);
-  }
-  if (slow) {   // the plan-driven instantiations that also serve speeds below 1 (MC + 2)
-#define SPX_FN_SLOW(M, C) (maxC > 1 ? reinterpret_cast<const void*>(spx_walk_fast_kernel<M, C, 0, 0, 3>) : reinterpret_cast<const void*>(spx_walk_fast_kernel<M, C, 0, 0, 2>))
-    fn = nwm == 8 ? SPX_FN_SLOW(8, 4) : nwm == 2 ? SPX_FN_SLOW(2, 0) : (nwc >= 4 ? SPX_FN_SLOW(4, 4) : SPX_FN_SLOW(4, 0));
-#undef SPX_FN_SLOW
-    return spx_kernel_vgprs(fn, scratch_bytes);
-  }
-#define SPX_FN_RM(M, C, MCV) (P.rate == 16000 && wcap == SPX_CT_WCAP_OF(M, C) ? reinterpret_cast<const void*>(spx_walk_fast_kernel<M, C, 16000, 0, MCV>) \
-                        : P.rate == 22050 && wcap == SPX_CT_WCAP_OF(M, C) ? reinterpret_cast<const void*>(spx_walk_fast_kernel<M, C, 22050, 0, MCV>) \
-                        : reinterpret_cast<const void*>(spx_walk_fast_kernel<M, C, 0, 0, MCV>))
-#define SPX_FN_R(M, C) (maxC > 1 ? SPX_FN_RM(M, C, 1) : SPX_FN_RM(M, C, 0))
-  if (nwm == 4 && nwc >= 4 && wcap == SPX_CT_WCAP_LONG && (P.rate == 16000 || P.rate == 22050))
-    fn = P.rate == 16000 ? (maxC > 1 ? reinterpret_cast<const void*>(spx_walk_fast_kernel<4, 4, 16000, 1, 1>) : reinterpret_cast<const void*>(spx_walk_fast_kernel<4, 4, 16000, 1, 0>))
-                         : (maxC > 1 ? reinterpret_cast<const void*>(spx_walk_fast_kernel<4, 4, 22050, 1, 1>) : reinterpret_cast<const void*>(spx_walk_fast_kernel<4, 4, 22050, 1, 0>));
-  // the forms spx_walk_config selects (SPX_FAST_FORMS below)
-  else if (nwm == 8) fn = maxC > 1 ? reinterpret_cast<const void*>(spx_walk_fast_kernel<8, 4, 0, 0, 1>) : reinterpret_cast<const void*>(spx_walk_fast_kernel<8, 4, 0, 0, 0>);
-  else if (nwm == 2) fn = SPX_FN_R(2, 0);
-  else fn = nwc >= 4 ? SPX_FN_R(4, 4) : SPX_FN_R(4, 0);
-#undef SPX_FN_R
-#undef SPX_FN_RM
-  return spx_kernel_vgprs(fn, scratch_bytes);
-}
-
-void spx_launch_walk_fast(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, const int16_t* in,
-                          int16_t* out, int64_t* n_out, SpxStreamState* states, const float* scratch,
-                          const int* speed_ready, int nwm, int nwc, int wcap, int maxC, hipStream_t st, size_t lds_min, bool slow) {
-  if (n_streams <= 0) return;
-  const FastLds LY = fast_lds_layout(P, wcap);
-  // lds_min: the caller wants these workgroups ONE to a CU (it asks for more than half a CU's LDS): walk kernels of several
-  // groups launched side by side otherwise land two to a CU here and there, and those chains end the call (spx_engine.hip)
-  const size_t lds_req = (size_t)LY.total > lds_min ? (size_t)LY.total : lds_min;
-#define SPX_LAUNCH_FAST_RSM(M, C, R, SPECV, MCV)                                                                               \
-  hipLaunchKernelGGL((spx_walk_fast_kernel<M, C, R, SPECV, MCV>), dim3(n_streams), dim3(64 * (M + C)), lds_req, st, P, streams, \
-                     in, out, n_out, states, scratch, speed_ready, wcap)
-#define SPX_LAUNCH_FAST_RS(M, C, R, SPECV)                                                                                \
-  do { if (maxC > 1) SPX_LAUNCH_FAST_RSM(M, C, R, SPECV, 1); else SPX_LAUNCH_FAST_RSM(M, C, R, SPECV, 0); } while (0)
-#define SPX_LAUNCH_FAST_R(M, C, R) SPX_LAUNCH_FAST_RS(M, C, R, 0)
-  // the two rates of the BASELINE configs get their own specialisation (with the default 4096-frame window)
-#define SPX_LAUNCH_FAST(M, C)                                              \
-  do {                                                                     \
-    if (P.rate == 16000 && wcap == SPX_CT_WCAP_OF(M, C)) SPX_LAUNCH_FAST_R(M, C, 16000);   \
-    else if (P.rate == 22050 && wcap == SPX_CT_WCAP_OF(M, C)) SPX_LAUNCH_FAST_R(M, C, 22050); \
-    else SPX_LAUNCH_FAST_R(M, C, 0);                                       \
-  } while (0)
+// The one place that maps a form (spx_walk_config: search waves, output waves, window frames) to an instantiation: the launch, the
+// register query and the kernel's name (spx_walk.hip, spx_diag.hip) all take it from here.
+// SPX_FAST_FORMS -- the forms spx_walk_config selects: 4 + 4 waves (one or two streams per CU; with the long window at the two
+// BASELINE rates), 4 + 0 (lean form, short jobs beyond one stream per CU), 2 + 0 (throughput form), each rate-specialised for
+// 16 / 22.05 kHz and generic, mono-only and multi-channel; 8 + 4 generic for the rates whose ragged refine tasks do not fit four
+// search waves (24 .. 32 kHz).  The other combinations (1 or 2 output waves, two search waves with an output wave, eight search
+// waves at a BASELINE rate) were A/B points of rounds 2 and 3 and are not instantiated.
+SpxKernelChoice spx_walk_fast_select(const SpxPlanDev& P, int nwm, int nwc, int wcap, int maxC, bool slow) {
+#define FAST_K(M, C, R, S, MCV) \
+  SpxKernelChoice{"spx_walk_fast_kernel", reinterpret_cast<const void*>(spx_walk_fast_kernel<M, C, R, S, MCV>), 64 * (M + C), 5, {M, C, R, S, MCV}}
+  // MC: 1 multi-channel, 0 mono-only; + 2 (LO = 2) the instantiations that also serve speeds below 1 (insertPitchPeriod)
+#define FAST_KC(M, C, R, S, LO) (maxC > 1 ? FAST_K(M, C, R, S, LO + 1) : FAST_K(M, C, R, S, LO))
+  // the two rates of the BASELINE configs have their own specialisation (with the form's default window)
+#define FAST_KRC(M, C, MCV) (P.rate == 16000 && wcap == SPX_CT_WCAP_OF(M, C) ? FAST_K(M, C, 16000, 0, MCV) \
+                             : P.rate == 22050 && wcap == SPX_CT_WCAP_OF(M, C) ? FAST_K(M, C, 22050, 0, MCV) : FAST_K(M, C, 0, 0, MCV))
+#define FAST_KR(M, C) (maxC > 1 ? FAST_KRC(M, C, 1) : FAST_KRC(M, C, 0))
+  static_assert(std::is_same<decltype(spx_walk_fast_kernel<4, 4, 0, 2, 3>), SpxWalkFastArgs>::value, "SpxWalkFastArgs is the kernel's argument list");
 #ifdef SPX_STAMPS
-  SPX_LAUNCH_FAST(4, 4);
-  return;
+  return FAST_KR(4, 4);   // the stamped build (tools/walk_stamps.py) always runs 4 + 4 waves
 #endif
+  // more than 64 coarse lags (11.025 kHz): the wide-coarse instantiations (SPEC = 2), plan-driven, 4 + 4 or 4 + 0 waves
+  // (spx_walk_fast_supports admits four search waves only there)
   if (fast_wide_coarse(P.minPeriod, P.maxPeriod, P.skip)) {
-    // more than 64 coarse lags (11.025 kHz): the wide-coarse instantiations (SPEC = 2), plan-driven, 4 + 4 or 4 + 0 waves
-    // (spx_walk_fast_supports admits four search waves only there)
-#define SPX_LAUNCH_WC(C)                                                                                                  \
-  do {                                                                                                                    \
-    if (slow) { if (maxC > 1) SPX_LAUNCH_FAST_RSM(4, C, 0, 2, 3); else SPX_LAUNCH_FAST_RSM(4, C, 0, 2, 2); }              \
-    else { if (maxC > 1) SPX_LAUNCH_FAST_RSM(4, C, 0, 2, 1); else SPX_LAUNCH_FAST_RSM(4, C, 0, 2, 0); }                   \
-  } while (0)
-    if (nwc >= 4) SPX_LAUNCH_WC(4); else SPX_LAUNCH_WC(0);
-#undef SPX_LAUNCH_WC
-    return;
+    if (nwc >= 4) return slow ? FAST_KC(4, 4, 0, 2, 2) : FAST_KC(4, 4, 0, 2, 0);
+    return slow ? FAST_KC(4, 0, 0, 2, 2) : FAST_KC(4, 0, 0, 2, 0);
   }
-  if (slow) {
-    // batches with slow-down jobs: the plan-driven instantiations with the insertPitchPeriod event (MC + 2), the forms
-    // spx_walk_config picks (4 + 4, 4 + 0, 2 + 0, 8 + 4)
-#define SPX_LAUNCH_SLOW(M, C) do { if (maxC > 1) SPX_LAUNCH_FAST_RSM(M, C, 0, 0, 3); else SPX_LAUNCH_FAST_RSM(M, C, 0, 0, 2); } while (0)
-    if (nwm == 8) SPX_LAUNCH_SLOW(8, 4);
-    else if (nwm == 2) SPX_LAUNCH_SLOW(2, 0);
-    else if (nwc >= 4) SPX_LAUNCH_SLOW(4, 4);
-    else SPX_LAUNCH_SLOW(4, 0);
-#undef SPX_LAUNCH_SLOW
-    return;
-  }
-  // SPX_FAST_FORMS -- the forms spx_walk_config selects: 4 + 4 waves (one or two streams per CU; with the long window at the two
-  // BASELINE rates), 4 + 0 (lean form, short jobs beyond one stream per CU), 2 + 0 (throughput form), each rate-specialised for
-  // 16 / 22.05 kHz and generic, mono-only and multi-channel; 8 + 4 generic for the rates whose ragged refine tasks do not fit four
-  // search waves (24 .. 32 kHz).  The other combinations (1 or 2 output waves, two search waves with an output wave, eight search
-  // waves at a BASELINE rate) were A/B points of rounds 2 and 3 and are not instantiated.
-  if (nwm == 4 && nwc >= 4 && wcap == SPX_CT_WCAP_LONG && (P.rate == 16000 || P.rate == 22050)) {
-    if (P.rate == 16000) SPX_LAUNCH_FAST_RS(4, 4, 16000, 1); else SPX_LAUNCH_FAST_RS(4, 4, 22050, 1);
-  } else if (nwm == 8) {
-    SPX_LAUNCH_FAST_R(8, 4, 0);
-  } else if (nwm == 2) {
-    SPX_LAUNCH_FAST(2, 0);
-  } else {
-    if (nwc >= 4) SPX_LAUNCH_FAST(4, 4);
-    else SPX_LAUNCH_FAST(4, 0);
-  }
-#undef SPX_LAUNCH_FAST
-#undef SPX_LAUNCH_FAST_RS
-#undef SPX_LAUNCH_FAST_RSM
-#undef SPX_LAUNCH_FAST_R
+  // batches with slow-down jobs: plan-driven, the forms spx_walk_config picks (4 + 4, 4 + 0, 2 + 0, 8 + 4)
+  if (slow) return nwm == 8 ? FAST_KC(8, 4, 0, 0, 2) : nwm == 2 ? FAST_KC(2, 0, 0, 0, 2) : nwc >= 4 ? FAST_KC(4, 4, 0, 0, 2) : FAST_KC(4, 0, 0, 0, 2);
+  // the long window (SPEC = 1)
+  if (nwm == 4 && nwc >= 4 && wcap == SPX_CT_WCAP_LONG && (P.rate == 16000 || P.rate == 22050))
+    return P.rate == 16000 ? FAST_KC(4, 4, 16000, 1, 0) : FAST_KC(4, 4, 22050, 1, 0);
+  if (nwm == 8) return FAST_KC(8, 4, 0, 0, 0);
+  if (nwm == 2) return FAST_KR(2, 0);
+  return nwc >= 4 ? FAST_KR(4, 4) : FAST_KR(4, 0);
+#undef FAST_KR
+#undef FAST_KRC
+#undef FAST_KC
+#undef FAST_K
 }
