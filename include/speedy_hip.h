@@ -152,7 +152,7 @@ int spx_batch_run_ahead_when(spx_plan_t plan, const spx_stream_job* jobs, int n_
                              int16_t* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
                              const spx_taps* taps, void* hip_stream, void* in_ready_event);
 
-/* ---- the owning pipeline (round 5): batch after batch of one shape, host memory to host memory ----
+/* ---- the owning pipeline (round 5): batch after batch, host memory to host memory ----
  * What the reference's caller loop does per stream -- write a chunk, read what is ready, again (speedy_wave.cc:154-242) -- for a
  * caller that feeds BATCHES: spx_pipeline_submit hands over one batch of input (host or device memory), spx_pipeline_wait returns
  * that batch's output.  The object OWNS everything in between: `depth` sets of device buffers (input, output, workspace), pinned
@@ -162,8 +162,9 @@ int spx_batch_run_ahead_when(spx_plan_t plan, const spx_stream_job* jobs, int n_
  * into pinned host memory -- no device-to-host copy is enqueued and no host thread waits inside submit, so copies in, kernels and
  * copies out of up to `depth` batches are in flight at once.  The relaxed stream order that spx_batch_run_overlapped asks its
  * caller to respect is an implementation detail here: nobody else can touch the buffers.
- *   jobs      the shape of every batch: n_in, channels, speed, nonlinear, feedback and in_off (where stream i starts in a batch's
- *             input, in int16 values); out_off / out_cap are ignored (the pipeline lays the outputs out itself, capacity =
+ *   jobs      the shape of every batch of spx_pipeline_submit, and the CAPACITY of the pipeline for spx_pipeline_submit_jobs: n_in,
+ *             channels, speed, nonlinear, feedback and in_off (where stream i -- lane i -- starts in a batch's input, in int16
+ *             values); out_off / out_cap are ignored (the pipeline lays the outputs out itself, capacity =
  *             spx_plan_out_capacity_for)
  *   plans / plan_index   as in spx_batch_run_mixed, for batches that mix sample rates (spx_pipeline_create: one plan)
  *   depth     buffer sets, 2 .. 8 (0 = the default, 4); 3 or more let the walk kernels of consecutive batches overlap fully
@@ -192,6 +193,36 @@ int16_t* spx_pipeline_host_input(spx_pipeline_t p);
  * spx_batch_* calls).  Returns the batch's ticket (0, 1, 2 ...) or a negative error.
  * At most `depth` batches are in flight: the call waits for the batch `depth` tickets back first. */
 int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_device);
+/* spx_pipeline_submit with THIS batch's job table.  The table given to spx_pipeline_create becomes the pipeline's CAPACITY: lane i
+ * takes any job that fits what lane i was created with.  (spx_pipeline_submit(p, in, d) is this call with the creation table.)
+ *   jobs   HOST array of exactly the n_streams the pipeline was created with; copied before the call returns.  Read: in_off, n_in,
+ *          speed, nonlinear, feedback and channels.  out_off / out_cap are ignored: the pipeline keeps the output layout and the
+ *          capacities of its creation and hands those to the engine.  channels must be the lane's channel count at creation; the
+ *          lane's plan (plan_index of a mixed pipeline) is fixed as well.  n_in = 0 is an empty lane (count 0, no room in the packed
+ *          output): a batch with fewer live streams than lanes.
+ * The table is accepted if and only if, for every lane,
+ *   - the job is one spx_batch_run takes (speed finite and > 0, nonlinear in [0, 1], feedback finite, fewer than 2^30 frames ...),
+ *   - in_off >= 0 and in_off + n_in * channels <= spx_pipeline_input_values(p),
+ *   - spx_plan_out_capacity_for(the lane's plan, n_in, speed, nonlinear) <= the lane's capacity at creation,
+ * and spx_batch_workspace_bytes (_mixed) of the table <= that of the creation table: the workspace grows with the number of analysis
+ * frames, so linear lanes turned nonlinear can exceed it where no lane exceeds its output capacity.
+ * SIZING: for speed >= 1 the capacity is n_in + slack whatever the speed -- a pipeline created with the longest n_in per lane and
+ * nonlinear = 1 admits every shorter job at any speed >= 1, linear or nonlinear.  A slow-down lane must be created with the
+ * smallest speed it will see (and nonlinear, if it will ever be: the nonlinear capacity of a slow-down assumes the 0.01 clamp).
+ * A table that is refused returns -1 with spx_last_error naming the lane and the limit, BEFORE anything is waited for, copied or
+ * enqueued: no ticket number is used up, batches in flight are untouched, the pipeline stays fully usable.
+ * HOST input is copied up to this batch's extent only -- max over lanes of in_off + n_in * channels -- and need not be longer; DEVICE
+ * input is allocated for spx_pipeline_input_values() + 64 values as always.  Values behind a short lane's end may hold another
+ * lane's samples or an earlier batch's: padding, whose content does not matter.
+ * Tickets, depth, spx_pipeline_wait, spx_pipeline_input_consumed and spx_pipeline_host_input as for spx_pipeline_submit; with
+ * SPX_PIPELINE_DEVICE_OUT the offsets stay the static capacity layout.  Results per stream are those of spx_batch_run on the same
+ * job and samples; fixed-shape and varying batches may be mixed freely on one pipeline.  (A table whose speed class differs from
+ * the previous batch's -- a lane at speed < 1 behind speed-up batches -- takes other walk kernels and may take another launch
+ * order: slower or faster, the same bytes.) */
+int64_t spx_pipeline_submit_jobs(spx_pipeline_t p, const spx_stream_job* jobs, const int16_t* in, int in_is_device);
+/* 0 if spx_pipeline_submit_jobs would accept this table, else -1 and spx_last_error names the lane and the limit.  Enqueues nothing,
+ * waits for nothing. */
+int spx_pipeline_jobs_fit(spx_pipeline_t p, const spx_stream_job* jobs);
 /* Blocks until the input handed over with `ticket` may be overwritten: the copy in has finished (host input), the batch's kernels
  * have finished (device input: they read it to the end).  0, or a negative error (unknown ticket). */
 int spx_pipeline_input_consumed(spx_pipeline_t p, int64_t ticket);

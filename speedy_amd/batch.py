@@ -339,16 +339,24 @@ class MixedBatch:
 
 
 class Pipeline:
-    """spx_pipeline (include/speedy_hip.h): batch after batch of ONE shape, host memory to host memory -- the library owns the
-    device buffer sets, the pinned output buffers, its streams and events, and overlaps copies in, kernels and copies out of up
-    to `depth` batches.  The caller loop of the reference (speedy_wave.cc:154-242: write a chunk, read what is ready) for a caller
-    whose unit is a batch of streams.
+    """spx_pipeline (include/speedy_hip.h): batch after batch, host memory to host memory -- the library owns the device buffer
+    sets, the pinned output buffers, its streams and events, and overlaps copies in, kernels and copies out of up to `depth`
+    batches.  The caller loop of the reference (speedy_wave.cc:154-242: write a chunk, read what is ready) for a caller whose unit
+    is a batch of streams.
 
         pipe = Pipeline(plan, lengths, channels, speed)
         t = pipe.submit(x)            # x: packed int16 input of one batch (numpy / pinned torch tensor; device tensor: device=True)
         outs = pipe.results(t)        # list of per-stream int16 arrays (copies); pipe.wait(t) returns the raw views
 
-    plans / plan_index: a batch that mixes sample rates (spx_pipeline_create_mixed)."""
+    The table given here is the pipeline's CAPACITY and the shape submit() runs; submit_jobs() hands over a batch with its own
+    lengths, speeds, nonlinear factors and feedback strengths per lane (spx_pipeline_submit_jobs): lane i takes any job that fits
+    what lane i was created with -- for speed >= 1 the capacity is n_in + slack whatever the speed, so lanes created with the
+    longest length and nonlinear = 1 take every shorter job at any speed >= 1, linear or nonlinear; a slow-down lane is created
+    with the smallest speed it will see.  A length of 0 is an empty lane (a batch with fewer streams than lanes).
+
+        t = pipe.submit_jobs(pipe.pack(xs, lens), lens, speed=speeds)
+
+    plans / plan_index: a batch that mixes sample rates (spx_pipeline_create_mixed); a lane's plan and channel count are fixed."""
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, depth=0, device_out=False, plan_index=None):
         plans = list(plan) if isinstance(plan, (list, tuple)) else [plan]
@@ -361,6 +369,7 @@ class Pipeline:
         nlv = np.broadcast_to(np.asarray(nonlinear, np.float32), (n,)).copy()
         fb = np.broadcast_to(np.asarray(feedback, np.float32), (n,)).copy()
         self.lengths, self.channels = np.asarray(lengths, np.int64), ch
+        self.speeds, self.nonlinears, self.feedbacks = sp, nlv, fb   # the creation values: what None means in submit_jobs
         self.jobs = (StreamJob * n)()
         self.in_offs = []
         in_off = 0
@@ -385,12 +394,14 @@ class Pipeline:
         assert self.L.spx_pipeline_input_values(self.h) == self.total_in or n == 0
         self._keep = {}   # ticket -> the input object (host memory must stay alive until its copy has been made)
 
-    def pack(self, streams):
-        """One batch's input as the pipeline expects it: the streams (int16 numpy arrays, interleaved) one after the other."""
+    def pack(self, streams, lengths=None):
+        """One batch's input as the pipeline expects it: the streams (int16 numpy arrays, interleaved) each at its lane's offset.
+        lengths: this batch's frames per lane (submit_jobs) -- shorter streams start where the lane starts."""
+        lengths = self.lengths if lengths is None else lengths
         host = np.zeros(self.total_in, np.int16)
         for i, x in enumerate(streams):
             x = np.ascontiguousarray(x, np.int16).ravel()
-            assert x.size == int(self.lengths[i]) * int(self.channels[i])
+            assert x.size == int(lengths[i]) * int(self.channels[i]) <= int(self.lengths[i]) * int(self.channels[i])
             host[self.in_offs[i]:self.in_offs[i] + x.size] = x
         return host
 
@@ -401,23 +412,57 @@ class Pipeline:
             raise RuntimeError("spx_pipeline_host_input: " + self.L.spx_last_error().decode())
         return np.ctypeslib.as_array((C.c_int16 * self.total_in).from_address(ptr))
 
-    def submit(self, x, device=False):
+    def _input_ptr(self, x, extent):
         if isinstance(x, torch.Tensor):
-            assert x.dtype == torch.int16 and x.is_contiguous() and x.numel() >= self.total_in
-            device = x.is_cuda
+            assert x.dtype == torch.int16 and x.is_contiguous() and x.numel() >= extent
             # (include/speedy_hip.h: a device input is used in place and must be allocated 64 values past the last stream's end)
-            assert not device or x.numel() >= self.total_in + 64, "device input: allocate spx_pipeline_input_values() + 64 int16 values"
-            ptr = x.data_ptr()
-        else:
-            x = np.ascontiguousarray(x, np.int16)
-            assert x.size >= self.total_in
-            ptr = x.ctypes.data
-        t = self.L.spx_pipeline_submit(self.h, ptr, 1 if device else 0)
+            assert not x.is_cuda or x.numel() >= self.total_in + 64, "device input: allocate spx_pipeline_input_values() + 64 int16 values"
+            return x, x.data_ptr(), x.is_cuda
+        x = np.ascontiguousarray(x, np.int16)
+        assert x.size >= extent
+        return x, x.ctypes.data, False
+
+    def _ticket(self, t, x, call):
         if t < 0:
-            raise RuntimeError("spx_pipeline_submit: " + self.L.spx_last_error().decode())
+            raise RuntimeError(call + ": " + self.L.spx_last_error().decode())
         self._keep[t] = x
         self._keep.pop(t - 2 * self.depth, None)
         return t
+
+    def submit(self, x, device=False):
+        x, ptr, dev = self._input_ptr(x, self.total_in)
+        device = dev if isinstance(x, torch.Tensor) else device
+        return self._ticket(self.L.spx_pipeline_submit(self.h, ptr, 1 if device else 0), x, "spx_pipeline_submit")
+
+    def table(self, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None):
+        """The job table of one batch (spx_stream_job[n], host): None = the value the lane was created with."""
+        n = self.n
+        assert len(lengths) == n
+        sp = self.speeds if speed is None else np.broadcast_to(np.asarray(speed, np.float32), (n,))
+        nlv = self.nonlinears if nonlinear is None else np.broadcast_to(np.asarray(nonlinear, np.float32), (n,))
+        fb = self.feedbacks if feedback is None else np.broadcast_to(np.asarray(feedback, np.float32), (n,))
+        offs = self.in_offs if in_offs is None else in_offs
+        jobs = (StreamJob * n)()
+        for i in range(n):
+            j = jobs[i]
+            j.in_off, j.n_in, j.out_off, j.out_cap = int(offs[i]), int(lengths[i]), 0, 0   # (the outputs stay where creation put them)
+            j.channels, j.speed, j.nonlinear, j.feedback = int(self.channels[i]), float(sp[i]), float(nlv[i]), float(fb[i])
+        return jobs
+
+    def fits(self, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None):
+        """Would submit_jobs accept this batch?  (spx_pipeline_jobs_fit: enqueues nothing, waits for nothing.)"""
+        return self.L.spx_pipeline_jobs_fit(self.h, self.table(lengths, speed, nonlinear, feedback, in_offs)) == 0
+
+    def submit_jobs(self, x, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None, device=False):
+        """submit() with THIS batch's lengths, speeds, nonlinear factors, feedback strengths and input offsets per lane (None = the
+        creation value).  A host input need only reach this batch's extent: max over lanes of in_off + length * channels.
+        RuntimeError with the library's text (the lane and the limit) for a batch that does not fit the pipeline."""
+        jobs = self.table(lengths, speed, nonlinear, feedback, in_offs)
+        # (at most the pipeline's input: a table that ends behind it is the library's to refuse, not an assertion's)
+        extent = min(self.total_in, max(int(j.in_off) + int(j.n_in) * int(j.channels) for j in jobs))
+        x, ptr, dev = self._input_ptr(x, extent)
+        device = dev if isinstance(x, torch.Tensor) else device
+        return self._ticket(self.L.spx_pipeline_submit_jobs(self.h, jobs, ptr, 1 if device else 0), x, "spx_pipeline_submit_jobs")
 
     def input_consumed(self, ticket):
         """Blocks until the input handed over with `ticket` may be overwritten (host input: copied in; device input: batch done)."""

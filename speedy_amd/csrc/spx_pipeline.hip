@@ -1,5 +1,12 @@
-// spx_pipeline (include/speedy_hip.h): batch after batch of one shape, host memory to host memory, with everything in between
-// owned by the library -- `depth` sets of device buffers, the pinned output buffers, two HIP streams, the events.
+// spx_pipeline (include/speedy_hip.h): batch after batch, host memory to host memory, with everything in between owned by the
+// library -- `depth` sets of device buffers, the pinned output buffers, two HIP streams, the events.
+//
+// The table given at creation is the pipeline's CAPACITY: where every lane's output lies (out_off), how many frames it holds
+// (out_cap), the lane's channel count and plan, the input's extent and the workspace size -- every buffer is sized from these and
+// none changes afterwards.  What a batch RUNS is a job table per ticket: the creation table itself (spx_pipeline_submit), or the
+// caller's for this batch (spx_pipeline_submit_jobs) once pipeline_check has found that every lane's job fits its lane.  The
+// engine takes a fresh table with every call anyway (run_impl rebuilds layout, speed class, launch mode and staged tables from
+// it), and the gather kernels read the counts from the device and the capacities from d_tab, which stays valid.
 //
 // What one submit enqueues (nothing waits on the host except for the batch `depth` tickets back):
 //   copy stream   wait(kernels of the batch that last used this buffer set)  ->  H2D of the input  ->  record(in)
@@ -21,6 +28,7 @@
 // per batch against 1.67 - 1.70.  Not kept.
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -105,6 +113,8 @@ struct SpxPipeSlot {
   int64_t* h_meta = nullptr;      // pinned: offsets[n + 1], counts[n]
   hipEvent_t ev_in = nullptr;     // the input has arrived in d_in
   hipEvent_t ev_done = nullptr;   // kernels and gather done: the output is in host memory, d_in / d_out may be reused
+  std::vector<spx_stream_job> jobs;   // the table this ticket was submitted with (the pipeline's out_off / out_cap in it): kept for the
+                                      // record -- the engine stages what it needs before its call returns, nothing reads this later
   int64_t ticket = -1;
   bool in_recorded = false;       // ev_in has been recorded at least once (h_in / d_in have a copy to wait for)
   bool in_host = false;           // this ticket's input came from host memory: consumed once ev_in has passed (device input: ev_done)
@@ -116,7 +126,8 @@ struct spx_pipeline {
   int n = 0, depth = 0;
   unsigned flags = 0;
   int device = 0;
-  std::vector<spx_stream_job> jobs;   // the caller's, with the pipeline's own out_off / out_cap
+  std::vector<spx_stream_job> jobs;   // the creation table with the pipeline's own out_off / out_cap: every lane's CAPACITY (out_off,
+                                      // out_cap, channels; with in_values and ws_bytes below), and the table of spx_pipeline_submit
   std::vector<int64_t> static_offsets;   // SPX_PIPELINE_DEVICE_OUT: the fixed layout of d_out (offsets[n] = its extent)
   size_t in_values = 0, out_values = 0, ws_bytes = 0;
   hipStream_t s_h2d = nullptr, s_run = nullptr;
@@ -258,15 +269,16 @@ int16_t* spx_pipeline_host_input(spx_pipeline_t p) {
   return S.h_in;
 }
 
-int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_device) {
-  if (!p || !in) return pfail(-1, "spx_pipeline_submit: bad arguments");
-  int cur = 0;
-  if (hipGetDevice(&cur) == hipSuccess && cur != p->device) return pfail(-1, "spx_pipeline_submit: the pipeline's device is not the current one");
+}  // extern "C"
+
+// One batch with the table `jobs` (the pipeline's own layout in it) and `extent` int16 values of input.
+static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, size_t extent, const int16_t* in, int in_is_device) {
   const int64_t ticket = p->next_ticket;
   SpxPipeSlot& S = p->slots[(size_t)(ticket % p->depth)];
   // at most `depth` batches in flight: the batch that last used this buffer set has finished (its output, if nobody asked for
   // it, is dropped here)
   if (S.ticket >= 0) PCHK(hipEventSynchronize(S.ev_done));
+  S.jobs.assign(jobs, jobs + p->n);
   const int16_t* dev_in = in;
   void* in_ready = nullptr;
   if (!in_is_device) {
@@ -279,7 +291,8 @@ int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_devic
       PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_in), (p->in_values + 64) * sizeof(int16_t)));
       PCHK(hipMemsetAsync(S.d_in, 0, (p->in_values + 64) * sizeof(int16_t), p->s_h2d));
     }
-    PCHK(hipMemcpyAsync(S.d_in, in, p->in_values * sizeof(int16_t), hipMemcpyHostToDevice, p->s_h2d));
+    // (this batch's extent only: what lies behind it in d_in -- an earlier batch's samples -- is padding no lane of this batch reads)
+    if (extent) PCHK(hipMemcpyAsync(S.d_in, in, extent * sizeof(int16_t), hipMemcpyHostToDevice, p->s_h2d));
     PCHK(hipEventRecord(S.ev_in, p->s_h2d));
     S.in_recorded = true;
     dev_in = S.d_in;
@@ -292,11 +305,11 @@ int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_devic
   bool event_recorded = false;
   if (p->mixed) {
     // (round 6: detached like a one-plan batch -- the groups' walk kernels on the library's walk streams, two calls' worth in flight)
-    rc = spx_internal_run_mixed(p->plans.data(), (int)p->plans.size(), p->jobs.data(), p->plan_index.data(), p->n, dev_in, S.d_out, S.d_nout,
+    rc = spx_internal_run_mixed(p->plans.data(), (int)p->plans.size(), S.jobs.data(), p->plan_index.data(), p->n, dev_in, S.d_out, S.d_nout,
                                 S.ws, p->ws_bytes, p->s_run, true, in_ready, host_out ? nullptr : S.ev_done, !host_out);
     event_recorded = !host_out;
   } else {
-    rc = spx_internal_run(p->plans[0], p->jobs.data(), p->n, dev_in, S.d_out, S.d_nout, S.ws, p->ws_bytes, nullptr, p->s_run, true, true, in_ready,
+    rc = spx_internal_run(p->plans[0], S.jobs.data(), p->n, dev_in, S.d_out, S.d_nout, S.ws, p->ws_bytes, nullptr, p->s_run, true, true, in_ready,
                           host_out ? nullptr : S.ev_done, !host_out);
     event_recorded = !host_out;
   }
@@ -322,6 +335,87 @@ int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_devic
   S.ticket = ticket;
   p->next_ticket++;
   return ticket;
+}
+
+static int lane_fail(int lane, const std::string& what) { return pfail(-1, "spx_pipeline: lane " + std::to_string(lane) + ": " + what); }
+
+// Does the caller's table fit the pipeline?  0 with `table` = the caller's jobs in the pipeline's own output layout and `extent` =
+// the int16 values of input the batch reads, or -1 with the lane and the limit in spx_last_error.  Host arithmetic only.
+// The limits are the pipeline's own: the lane's channel count, the input buffer, the lane's output capacity, the workspace.
+// A job's VALUES are the engine's to judge (build_streams, spx_engine.hip) -- but the engine judges inside a call, behind the wait
+// for the buffer set and the copy in, and a refusal here has to come before both: the rules on speed, nonlinear factor, feedback
+// strength and length are therefore asked here first, in the engine's words; the call itself still applies every rule it has.
+static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, std::vector<spx_stream_job>& table, size_t* extent) {
+  const int n = p->n;
+  table.assign(jobs, jobs + n);
+  size_t ext = 0;
+  for (int i = 0; i < n; i++) {
+    spx_stream_job& j = table[i];
+    const spx_stream_job& c = p->jobs[i];
+    if (j.channels != c.channels)
+      return lane_fail(i, std::to_string(j.channels) + " channels, the lane was created with " + std::to_string(c.channels));
+    if (j.n_in < 0 || j.in_off < 0) return lane_fail(i, "bad job (a negative count / offset)");
+    if (!(j.speed > 0.0f) || !std::isfinite(j.speed)) return lane_fail(i, "speed must be finite and > 0");
+    if (!(j.nonlinear >= 0.0f && j.nonlinear <= 1.0f)) return lane_fail(i, "nonlinear factor outside [0, 1]");
+    if (!std::isfinite(j.feedback)) return lane_fail(i, "feedback strength is not finite");
+    if (j.n_in >= (1ll << 30)) return lane_fail(i, "stream of 2^30 frames or more");
+    if ((uint64_t)j.in_off > p->in_values || (uint64_t)j.n_in * (uint64_t)j.channels > p->in_values - (uint64_t)j.in_off)
+      return lane_fail(i, "in_off " + std::to_string(j.in_off) + " + n_in " + std::to_string(j.n_in) + " x " + std::to_string(j.channels) +
+                              " channels ends behind the pipeline's input of " + std::to_string(p->in_values) + " values (spx_pipeline_input_values)");
+    const size_t end = (size_t)j.in_off + (size_t)j.n_in * (size_t)j.channels;
+    if (end > ext) ext = end;
+    const int64_t need = spx_plan_out_capacity_for(p->plans[p->mixed ? p->plan_index[i] : 0], j.n_in, j.speed, j.nonlinear);
+    if (need > c.out_cap)
+      return lane_fail(i, "n_in " + std::to_string(j.n_in) + " at speed " + std::to_string(j.speed) + (j.nonlinear != 0.0f ? " nonlinear" : " linear") +
+                              " needs an output capacity of " + std::to_string(need) + " frames (spx_plan_out_capacity_for), the lane was created with " +
+                              std::to_string(c.out_cap));
+    j.out_off = c.out_off;
+    j.out_cap = c.out_cap;
+  }
+  const size_t ws = p->mixed ? spx_batch_workspace_bytes_mixed(p->plans.data(), (int)p->plans.size(), table.data(), p->plan_index.data(), n)
+                             : spx_batch_workspace_bytes(p->plans[0], table.data(), n);
+  if (!ws) return -1;   // (the engine could not lay the table out: its own message stands)
+  if (ws > p->ws_bytes) {
+    // the workspace grows with the analysis frames of the nonlinear lanes: name the first lane that has more of them than it was created with
+    int lane = 0;
+    for (int i = 0; i < n; i++) {
+      spx_plan_t pl = p->plans[p->mixed ? p->plan_index[i] : 0];
+      const int64_t now = table[i].nonlinear != 0.0f ? spx_plan_frames(pl, table[i].n_in) : 0;
+      const int64_t then = p->jobs[i].nonlinear != 0.0f ? spx_plan_frames(pl, p->jobs[i].n_in) : 0;
+      if (now > then) { lane = i; break; }
+    }
+    return lane_fail(lane, "more analysis frames than the lane was created with (a linear lane turned nonlinear, or a longer one): the batch needs a workspace of " +
+                               std::to_string(ws) + " bytes (spx_batch_workspace_bytes), the pipeline's holds " + std::to_string(p->ws_bytes));
+  }
+  *extent = ext;
+  return 0;
+}
+static int pipeline_current(spx_pipeline_t p, const char* who) {
+  int cur = 0;
+  if (hipGetDevice(&cur) == hipSuccess && cur != p->device) return pfail(-1, std::string(who) + ": the pipeline's device is not the current one");
+  return 0;
+}
+
+extern "C" {
+
+int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_device) {
+  if (!p || !in) return pfail(-1, "spx_pipeline_submit: bad arguments");
+  if (pipeline_current(p, "spx_pipeline_submit")) return -1;
+  return pipeline_submit(p, p->jobs.data(), p->in_values, in, in_is_device);
+}
+int spx_pipeline_jobs_fit(spx_pipeline_t p, const spx_stream_job* jobs) {
+  if (!p || !jobs) return pfail(-1, "spx_pipeline_jobs_fit: bad arguments");
+  std::vector<spx_stream_job> table;
+  size_t extent = 0;
+  return pipeline_check(p, jobs, table, &extent);
+}
+int64_t spx_pipeline_submit_jobs(spx_pipeline_t p, const spx_stream_job* jobs, const int16_t* in, int in_is_device) {
+  if (!p || !jobs || !in) return pfail(-1, "spx_pipeline_submit_jobs: bad arguments");
+  if (pipeline_current(p, "spx_pipeline_submit_jobs")) return -1;
+  std::vector<spx_stream_job> table;
+  size_t extent = 0;
+  if (pipeline_check(p, jobs, table, &extent)) return -1;   // (before anything is waited for, copied or enqueued: no ticket is used up)
+  return pipeline_submit(p, table.data(), extent, in, in_is_device);
 }
 
 static SpxPipeSlot* slot_of(spx_pipeline_t p, int64_t ticket) {
