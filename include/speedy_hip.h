@@ -110,6 +110,34 @@ size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* job
 /* spx_plan_out_capacity_for behind the rate stage: safe capacity in FINAL frames; -1 (spx_last_error) for a rate that is refused. */
 int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate);
 
+/* spx_batch_run_rate on FLOAT samples in device memory (sonicWriteFloatToStream / sonicReadFloatFromStream, sonic2.h:64-68).
+ *   in   DEVICE  float input samples in (-1, 1), 4-byte aligned; read once, exactly the jobs' values: no padding behind the end
+ *   out  DEVICE  float output samples, 4-byte aligned (every value an int16 / 32767.0f, the IEEE quotient)
+ * The job table is the same 48-byte table: in_off / out_off count FLOAT VALUES inside in / out, n_in / out_cap are frames as always,
+ * capacities come from spx_plan_out_capacity_for / _rate unchanged.  rates == NULL: every rate 1.  n_out has exactly
+ * spx_batch_run_rate's meaning: negative = out_cap was too small, and then exactly out_cap frames were written.
+ * The INPUT SCALE is per job, as the reference has it: nonlinear != 0 gives (double)x * 32768.0 (soniclib.c:496), nonlinear == 0
+ * gives x * 32767.0f in float (the TSM dependency's own scale).  The conversion to int16 is DEFINED here, because the C cast is
+ * undefined outside the short range: truncate toward zero to a 32-bit integer and keep the low 16 bits -- what the streaming API's
+ * host loop does on x86; full scale 1.0f on a nonlinear job gives -32768 -- and a product that is NaN or of magnitude >= 2^31
+ * gives 0.
+ * A layer on top of the int16 call: the call enqueues, on hip_stream and without a host wait, the job table's way into the
+ * workspace and the input conversion, then spx_batch_run_rate (spx_batch_run when every rate is 1: the int16 work is that call's,
+ * bit for bit) on int16 stagings inside the workspace, then the output conversion, which reads n_out on the device.  Taps are
+ * passed through.  The workspace (spx_batch_workspace_bytes_float, 256-byte aligned as every device allocation is) begins with the
+ * int16 call's own workspace, so spx_batch_read_steps works on it; behind it lie the table and the two stagings.
+ * Refused with -1 and spx_last_error, nothing launched: everything the int16 call refuses (a bad speed, rate, nonlinear factor ...),
+ * a null pointer, in or out not 4-byte aligned, a workspace that is too small.
+ * NOT offered on float samples: the _ahead / _overlapped / _mixed* forms, the pipeline object, spx_batch_pack_outputs. */
+size_t spx_batch_workspace_bytes_float(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams);
+int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, const float* in,
+                        float* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
+                        const spx_taps* taps, void* hip_stream);
+/* The two conversions on their own, n contiguous values, asynchronous on hip_stream.
+ * nonlinear_scale != 0: the 32768.0 double scale, else 32767.0f. */
+int spx_float_to_short(const float* in, int16_t* out, size_t n, int nonlinear_scale, void* hip_stream);
+int spx_short_to_float(const int16_t* in, float* out, size_t n, void* hip_stream);
+
 /* spx_batch_run for a caller that issues batch after batch (round 4): consecutive calls are software-pipelined.  This call's
  * analysis and tension kernels are enqueued on a stream of the library's and start AT ONCE -- beside the walk kernel of the
  * previous call, which is still running on hip_stream -- and its own walk kernel follows on hip_stream with every speed ready.

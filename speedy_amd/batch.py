@@ -216,6 +216,119 @@ class Batch:
         return r
 
 
+class FloatBatch(Batch):
+    """Batch on FLOAT samples in (-1, 1) (spx_batch_run_float: sonicWriteFloatToStream / sonicReadFloatFromStream for audio that is
+    already in device memory).  d_in / d_out are torch.float32 tensors packed like Batch's -- the same job table, offsets in
+    float values -- and the int16 work in between is Batch's, bit for bit: the input is scaled per job as the reference scales it
+    (nonlinear != 0: x * 32768.0 in double, else x * 32767.0f) and truncated, every output value is an int16 / 32767.0f.
+    rate: as Batch has it.  The plain call only: no run_ahead, no pack_outputs."""
+
+    def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
+                 spectrogram_taps=False, rate=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
+        self.plan = plan
+        n = len(lengths)
+        self.n = n
+        self.rates = None
+        if rate is not None:
+            self.rates = np.ascontiguousarray(np.broadcast_to(np.asarray(rate, np.float32), (n,)))
+        ch = np.broadcast_to(np.asarray(channels, np.int32), (n,)).copy()
+        sp = np.broadcast_to(np.asarray(speed, np.float32), (n,)).copy()
+        nlv = np.broadcast_to(np.asarray(nonlinear, np.float32), (n,)).copy()
+        fb = np.broadcast_to(np.asarray(feedback, np.float32), (n,)).copy()
+        self.lengths = np.asarray(lengths, np.int64)
+        self.channels = ch
+        self.jobs = (StreamJob * n)()
+        in_off = out_off = fo = 0
+        self.in_offs, self.out_offs, self.out_caps, self.frame_offs, self.frames = [], [], [], [], []
+        for i in range(n):
+            cap = plan.out_capacity(int(self.lengths[i]), float(sp[i]), float(nlv[i]),
+                                    None if self.rates is None else float(self.rates[i]))
+            j = self.jobs[i]
+            j.in_off, j.n_in, j.out_off, j.out_cap = in_off, int(self.lengths[i]), out_off, cap
+            j.channels, j.speed, j.nonlinear, j.feedback = int(ch[i]), float(sp[i]), float(nlv[i]), float(fb[i])
+            self.in_offs.append(in_off)
+            self.out_offs.append(out_off)
+            self.out_caps.append(cap)
+            T = plan.frames(int(self.lengths[i])) if nlv[i] != 0 else 0
+            self.frame_offs.append(fo)
+            self.frames.append(T)
+            fo += T
+            in_off += int(self.lengths[i]) * int(ch[i])
+            out_off += cap * int(ch[i])
+        self.total_in, self.total_out, self.total_frames = in_off, out_off, fo
+        dev = torch.device(device)
+        self.device = dev
+        self.d_in = torch.zeros(max(1, in_off), dtype=torch.float32, device=dev)   # (no padding: the conversion reads the jobs' values only)
+        self.d_out = torch.zeros(max(1, out_off), dtype=torch.float32, device=dev)
+        self.d_nout = torch.zeros(n, dtype=torch.int64, device=dev)
+        wsb = plan.L.spx_batch_workspace_bytes_float(plan.h, self.jobs, self._rates_ptr(), n)
+        if wsb == 0:
+            raise RuntimeError("spx_batch_workspace_bytes_float: " + plan.L.spx_last_error().decode())
+        self.d_ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
+        self.taps = None
+        if taps:
+            T1 = max(1, fo)
+            self.t_tension = torch.zeros(T1, dtype=torch.float32, device=dev)
+            self.t_speed = torch.zeros(T1, dtype=torch.float32, device=dev)
+            self.t_features = torch.zeros(T1 * 15, dtype=torch.float32, device=dev)
+            self.taps = Taps(self.t_tension.data_ptr(), self.t_speed.data_ptr(), self.t_features.data_ptr(), None, None)
+            if spectrogram_taps:
+                self.t_spec = torch.zeros(T1 * plan.N, dtype=torch.float32, device=dev)
+                self.t_norm = torch.zeros(T1 * plan.W, dtype=torch.float32, device=dev)
+                self.taps.spectrogram = self.t_spec.data_ptr()
+                self.taps.normalized = self.t_norm.data_ptr()
+
+    def _rates_ptr(self):
+        return None if self.rates is None else self.rates.ctypes.data_as(C.POINTER(C.c_float))
+
+    def upload(self, streams):
+        """streams: list of float32 numpy arrays (interleaved).  Packs and copies them to HBM."""
+        host = np.zeros(self.d_in.numel(), np.float32)
+        for i, x in enumerate(streams):
+            x = np.ascontiguousarray(x, np.float32).ravel()
+            assert x.size == int(self.lengths[i]) * int(self.channels[i])
+            host[self.in_offs[i]:self.in_offs[i] + x.size] = x
+        self.d_in.copy_(torch.from_numpy(host))
+
+    def set_input(self, tensor):
+        """A float32 CUDA tensor that is already packed (stream i at in_offs[i]) becomes the input: no copy, no padding needed."""
+        if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype == torch.float32 and tensor.is_contiguous()):
+            raise ValueError("set_input: a contiguous float32 CUDA tensor")
+        if tensor.device != self.d_in.device or tensor.numel() < self.total_in:
+            raise ValueError("set_input: the tensor is on another device or shorter than the batch's %d values" % self.total_in)
+        self.d_in = tensor
+
+    def run(self, stream=None):
+        """Enqueue input conversion, the int16 call and output conversion on `stream` (torch stream or None)."""
+        hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        rc = self.plan.L.spx_batch_run_float(self.plan.h, self.jobs, self._rates_ptr(), self.n, self.d_in.data_ptr(),
+                                             self.d_out.data_ptr(), self.d_nout.data_ptr(), self.d_ws.data_ptr(),
+                                             self.d_ws.numel(), C.byref(self.taps) if self.taps is not None else None, hs)
+        if rc != 0:
+            raise RuntimeError("spx_batch_run_float: " + self.plan.L.spx_last_error().decode())
+
+    def run_ahead(self, stream=None, in_ready=None, overlap=False):
+        raise RuntimeError("a float batch runs through the plain call only (spx_batch_run_float)")
+
+    def pack_outputs(self, stream=None):
+        raise RuntimeError("spx_batch_pack_outputs packs int16 outputs; a float batch has none")
+
+    def results(self):
+        """Synchronise and return per-stream float32 outputs (host numpy)."""
+        torch.cuda.synchronize(self.device)
+        nout = self.d_nout.cpu().numpy()
+        lost = nout == np.iinfo(np.int64).min   # SPX_NOUT_LOST_PRODUCER
+        if lost.any():
+            raise RuntimeError("a producer kernel never delivered its frames to streams %s (device-side poll limit)"
+                               % np.nonzero(lost)[0][:8])
+        if (nout < 0).any():
+            raise RuntimeError("output capacity exceeded for streams %s" % np.nonzero(nout < 0)[0][:8])
+        return [self.d_out[self.out_offs[i]:self.out_offs[i] + int(nout[i]) * int(self.channels[i])].cpu().numpy().copy()
+                for i in range(self.n)]
+
+
 class MixedBatch:
     """Streams of DIFFERENT sample rates in one call (spx_batch_run_mixed): stream i is served by plans[plan_index[i]].
     Inputs and outputs are packed like Batch's; results() returns the outputs in the order the streams were given."""
@@ -519,6 +632,18 @@ def compress_batch(streams, sample_rate, channels, speed, nonlinear=1.0, feedbac
     ch = np.broadcast_to(np.asarray(channels, np.int32), (len(streams),))
     lengths = [np.asarray(x).size // int(c) for x, c in zip(streams, ch)]
     b = Batch(plan, lengths, channels, speed, nonlinear, feedback, taps=taps, spectrogram_taps=spectrogram_taps, rate=rate)
+    b.upload(streams)
+    b.run()
+    return b.results(), b
+
+
+def compress_batch_float(streams, sample_rate, channels, speed, nonlinear=1.0, feedback=0.0, match_matlab=False,
+                         taps=False, spectrogram_taps=False, rate=None):
+    """compress_batch on float32 streams in (-1, 1): returns (list of float32 outputs, FloatBatch)."""
+    plan = Plan(sample_rate, match_matlab)
+    ch = np.broadcast_to(np.asarray(channels, np.int32), (len(streams),))
+    lengths = [np.asarray(x).size // int(c) for x, c in zip(streams, ch)]
+    b = FloatBatch(plan, lengths, channels, speed, nonlinear, feedback, taps=taps, spectrogram_taps=spectrogram_taps, rate=rate)
     b.upload(streams)
     b.run()
     return b.results(), b

@@ -813,6 +813,23 @@ int spx_internal_run(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
   return run_split(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, o);
 }
 
+// What a batch call refuses about its job table -- counts and offsets, speed, nonlinear factor, feedback, the sample rate's and the
+// channel count's LDS limits -- WITHOUT the call: spx_batch_run_float (spx_convert.hip) asks before it enqueues its input conversion,
+// so that a call that is refused has launched nothing.  rate_call: at least one rate other than 1 (the general walk kernel's window).
+int spx_internal_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call) {
+  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+  SpxPlanDev d = plan->dev;
+  if (d.tile_frames < 1) d.tile_frames = spx_analysis_small_tile_frames();
+  std::vector<SpxStreamDev> sv;
+  std::vector<int> tiles;
+  if (build_streams(d, jobs, n, 1, sv, tiles)) return -1;
+  const SpxSpeedClass SC = speed_class(jobs, n);
+  std::lock_guard<std::mutex> plan_lock(plan->mu);
+  const SpxModeResources& R = mode_resources(plan, n, SC.maxC, SC.speedup_only && !rate_call, SC.any_speed && !rate_call);
+  if (R.walk.lds > 160 * 1024) return fail(-1, "spx_batch: too many channels for the walk kernel's LDS window");
+  return 0;
+}
+
 extern "C" {
 // (the larger of the one-call layout and the sub-batch layouts: which of the two a spx_batch_run takes is decided per call)
 size_t spx_batch_workspace_bytes(spx_plan_t plan, const spx_stream_job* jobs, int n_streams) {
