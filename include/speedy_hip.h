@@ -85,7 +85,15 @@ size_t spx_batch_workspace_bytes(spx_plan_t plan, const spx_stream_job* jobs, in
  *   in   DEVICE  int16 input samples (read once)
  *   out  DEVICE  int16 output samples (written once)
  *   n_out DEVICE int64[n_streams]: produced frames per stream (negative = out_cap overflow)
- * Returns 0 when the launches were enqueued. */
+ * Returns 0 when the launches were enqueued.
+ * The reference stores any float as speed, nonlinear factor or feedback strength and has no defined behaviour for most of them.
+ * Here a job is taken if channels >= 1, no count or offset is negative, the speed is finite and > 0, the nonlinear factor lies in
+ * [0, 1], the feedback strength is finite, n_in < 2^30 and -- a nonlinear job -- the plan's analysis tile fits one CU's LDS;
+ * a batch if the walk kernel's window of its largest channel count fits a CU's LDS.  The whole table is judged by these rules
+ * before anything is enqueued: -1 with the first broken rule in spx_last_error, nothing launched, the plan as it was.  That
+ * holds for every batch call below -- _ahead / _overlapped (also where the call is cut into sub-batches), _mixed*, _rate, _float:
+ * the bad job may be the last of the last group -- and the rate / float workspace and capacity queries answer 0 / -1 for such
+ * a table; spx_pipeline_create* and spx_pipeline_submit_jobs / _jobs_fit apply the same rules per lane and name the lane. */
 int spx_batch_run(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int16_t* in,
                   int16_t* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
                   const spx_taps* taps, void* hip_stream);
@@ -105,9 +113,10 @@ int spx_batch_run(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, co
 int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, const int16_t* in,
                        int16_t* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
                        const spx_taps* taps, void* hip_stream);
-/* 0 (spx_last_error) for a rate spx_batch_run_rate would refuse. */
+/* 0 (spx_last_error) for a rate or a job spx_batch_run_rate would refuse. */
 size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams);
-/* spx_plan_out_capacity_for behind the rate stage: safe capacity in FINAL frames; -1 (spx_last_error) for a rate that is refused. */
+/* spx_plan_out_capacity_for behind the rate stage: safe capacity in FINAL frames; -1 (spx_last_error) for a rate, speed,
+ * nonlinear factor or n_in that is refused. */
 int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate);
 
 /* spx_batch_run_rate on FLOAT samples in device memory (sonicWriteFloatToStream / sonicReadFloatFromStream, sonic2.h:64-68).
@@ -199,6 +208,7 @@ int spx_batch_run_ahead_when(spx_plan_t plan, const spx_stream_job* jobs, int n_
  *   flags     SPX_PIPELINE_DEVICE_OUT: the outputs stay in device memory (no gather, no copy out).  Such a pipeline's calls are
  *             detached from its run stream, and since round 6 that holds for mixed-rate batches too: the groups' walk kernels of
  *             consecutive batches overlap on the library's walk streams (BASELINE configs[4] shard: 1.87 - 1.97 -> 1.56 ms per batch)
+ * NULL with spx_last_error ("spx_pipeline: lane N: " and the rule) for a creation table with a job spx_batch_run would refuse.
  * Not thread-safe: one host thread (or external locking) per pipeline; several pipelines may be alive at once. */
 typedef struct spx_pipeline* spx_pipeline_t;
 #define SPX_PIPELINE_DEVICE_OUT 1u

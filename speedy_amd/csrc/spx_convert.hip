@@ -149,18 +149,19 @@ static int64_t conv_blocks(int64_t vals) {
 // touch) | the int16 output staging, max(out_off + out_cap * channels) values; every part on a 256-byte boundary.
 struct FloatLayout { size_t base, off_table, off_in, off_out, total; };
 static int float_layout(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, FloatLayout& FL) {
-  if (!plan || !jobs || n < 1) return fail(-1, "spx_batch: bad arguments");
+  // everything the int16 call refuses about a job or a rate, once: with rates, spx_batch_workspace_bytes_rate asks (0 with the message)
+  if (!rates && spx_check_jobs(plan, jobs, n)) return -1;
+  FL.base = spx_batch_workspace_bytes_rate(plan, jobs, rates, n);
+  if (FL.base == 0) return -1;
   int64_t in_vals = 0, out_vals = 0;
   for (int i = 0; i < n; i++) {
     const spx_stream_job& j = jobs[i];
-    if (j.channels < 1 || j.n_in < 0 || j.in_off < 0 || j.out_off < 0 || j.out_cap < 0 || j.n_in >= (1ll << 30) ||
-        j.in_off >= (1ll << 46) || j.out_off >= (1ll << 46) || j.out_cap >= (1ll << 40) || j.channels > (1 << 15))
-      return fail(-1, "spx_batch: bad job (channels < 1, a negative count / offset, or a stream too long)");
+    // the float path's own limits: the stagings' extents below must not overflow
+    if (j.in_off >= (1ll << 46) || j.out_off >= (1ll << 46) || j.out_cap >= (1ll << 40) || j.channels > (1 << 15))
+      return fail(-1, "spx_batch: bad job (an offset of 2^46, a capacity of 2^40 or more than 2^15 channels: too large for the float call's stagings)");
     in_vals = std::max(in_vals, j.in_off + j.n_in * j.channels);
     out_vals = std::max(out_vals, j.out_off + j.out_cap * j.channels);
   }
-  FL.base = spx_batch_workspace_bytes_rate(plan, jobs, rates, n);   // (0 with the rate's message for a rate that is refused)
-  if (FL.base == 0) return -1;
   size_t o = (FL.base + 255) & ~(size_t)255;
   FL.off_table = o; o += (sizeof(SpxConvJob) * (size_t)n + 255) & ~(size_t)255;
   FL.off_in = o;    o += (sizeof(int16_t) * (size_t)(in_vals + 64) + 255) & ~(size_t)255;
@@ -216,10 +217,7 @@ int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float
     return fail(-1, "spx_batch_run_float: in and out must be 4-byte aligned");
   if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(-1, "spx_batch_run_float: the workspace must be 256-byte aligned");
   FloatLayout FL;
-  if (float_layout(plan, jobs, rates, n, FL)) return -1;   // bad counts / offsets, a rate that is refused
-  bool any_rate = false;
-  if (rates) for (int i = 0; i < n; i++) any_rate = any_rate || rates[i] != 1.0f;
-  if (spx_internal_check_jobs(plan, jobs, n, any_rate)) return -1;   // bad speed, nonlinear factor, feedback, channel count
+  if (float_layout(plan, jobs, rates, n, FL)) return -1;   // a job or a rate that is refused
   if (ws_bytes < FL.total) return fail(-1, "spx_batch_run_float: workspace too small (spx_batch_workspace_bytes_float)");
   hipStream_t st = static_cast<hipStream_t>(hs);
   unsigned char* w = static_cast<unsigned char*>(ws);

@@ -20,6 +20,7 @@
 
 #include "../../include/speedy_hip.h"
 #include "spx_internal.h"
+#include "spx_jobs.h"
 #include "spx_mode.h"
 
 #ifndef M_PI
@@ -214,5 +215,7 @@ struct SpxCallOpts {
 };
 int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out, void* ws, size_t ws_bytes,
              const spx_taps* taps, void* hs, bool do_a, bool do_w, const SpxCallOpts& opt = SpxCallOpts());
-int spx_internal_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call);   // a call's refusals, nothing launched
+// what a call refuses about its job table (spx_jobs.h, then the walk kernel's LDS window), asked before anything is enqueued
+SpxJobLimits spx_job_limits(spx_plan_t plan);
+int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call = false, bool short_window = false);
 int spx_read_steps(const SpxPlanDev& d, const spx_stream_job* jobs, int n, const void* ws, int32_t* steps, hipStream_t st);

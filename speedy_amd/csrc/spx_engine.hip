@@ -127,28 +127,17 @@ Layout layout_for(const SpxPlanDev& d, const spx_stream_job* jobs, int n) {
 
 // Job tables for `nch` consecutive time chunks of every stream: chunk c covers the input up to n_c frames
 // (n_c = n_in for the last chunk), starts where chunk c-1 stopped (frame_begin) and carries the state record.
-static int build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n, int nch,
-                         std::vector<SpxStreamDev>& v, std::vector<int>& tiles_per_chunk, const SpxRateCall* rc = nullptr) {
+// Fills tables, judges nothing: the jobs have passed spx_check_jobs at the call's top.
+static void build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n, int nch,
+                          std::vector<SpxStreamDev>& v, std::vector<int>& tiles_per_chunk, const SpxRateCall* rc = nullptr) {
   v.resize((size_t)n * nch);
   tiles_per_chunk.assign(nch, 0);
   int64_t fo = 0;
   const int TF = d.tile_frames;
   for (int i = 0; i < n; i++) {
     const spx_stream_job& j = jobs[i];
-    if (j.channels < 1 || j.n_in < 0 || j.in_off < 0 || j.out_off < 0 || j.out_cap < 0)
-      return fail(-1, "spx_batch: bad job (channels < 1 or a negative count / offset)");
-    // The reference takes any float here and has no defined behaviour for most of them (a speed <= 0 makes the TSM
-    // stage's step counts negative).  A job is refused unless every speed the TSM stage can be given is positive:
-    if (!(j.speed > 0.0f) || !std::isfinite(j.speed)) return fail(-1, "spx_batch: speed must be finite and > 0");
-    if (!(j.nonlinear >= 0.0f && j.nonlinear <= 1.0f))
-      return fail(-1, "spx_batch: nonlinear factor outside [0, 1] (sonic2.h:73-76; the blended speed could reach 0)");
-    if (!std::isfinite(j.feedback)) return fail(-1, "spx_batch: feedback strength is not finite");
-    if (j.nonlinear != 0.0f && !spx_internal_analysis_fits(d))
-      return fail(-1, "spx_batch: sample rate too high for the nonlinear path (the analysis tile does not fit one CU's LDS); linear jobs only");
-    if (j.n_in >= (1ll << 30)) return fail(-1, "spx_batch: stream of 2^30 frames or more (in-kernel positions are 32-bit)");
     const bool nonlinear = j.nonlinear != 0.0f;
     const int64_t Ttot = nonlinear ? frames_for(d, j.n_in) : 0;
-    if (Ttot > 0x7fffff00) return fail(-1, "spx_batch: stream too long");
     int64_t Tprev = 0;
     for (int c = 0; c < nch; c++) {
       int64_t n_c = j.n_in;
@@ -171,7 +160,6 @@ static int build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n,
     }
     fo += Ttot;
   }
-  return 0;
 }
 
 static SpxTapsDev taps_of(const spx_taps* t) {
@@ -454,9 +442,10 @@ struct SpxTimed {
 int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
              int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs, bool do_a,
              bool do_w, const SpxCallOpts& opt) {
-  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
-  SpxRange range_(do_a && do_w ? "spx_batch_run" : (do_a ? "spx_batch_analyze" : "spx_batch_walk"));
   const SpxForce* force = opt.force;
+  // the choke point every call passes: a table that is refused has changed nothing of the plan and enqueued nothing
+  if (spx_check_jobs(plan, jobs, n, opt.rate != nullptr, force && force->no_exclusive)) return -1;
+  SpxRange range_(do_a && do_w ? "spx_batch_run" : (do_a ? "spx_batch_analyze" : "spx_batch_walk"));
   SpxPlanDev d = plan->dev;  // a copy: the tile size is chosen per call
   Layout L = layout_for(d, jobs, n);
   if (ws_bytes < L.total || !ws) return fail(-1, "spx_batch: workspace too small");
@@ -478,8 +467,6 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   //     turns "doubtful", goes to the timed trial and ends in the concurrent mode: 1.69 -> 2.9 ms through the pipeline object).
   const bool short_window_res = opt.force && opt.force->no_exclusive;
   const SpxModeResources& R = mode_resources(plan, n, maxC, speedup_only, any_speed, short_window_res);
-  if (R.walk.lds > 160 * 1024)   // one CU's LDS; the window holds every channel of maxRequired + 64 frames at least
-    return fail(-1, "spx_batch: too many channels for the walk kernel's LDS window");
   hipStream_t st = static_cast<hipStream_t>(hs);
   // ---- decide ----
   SpxModeShape S;
@@ -533,8 +520,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   // ---- execute ----
   std::vector<SpxStreamDev> sv;
   std::vector<int> tiles;
-  int rc = build_streams(d, jobs, n, nch, sv, tiles, opt.rate);
-  if (rc) return rc;
+  build_streams(d, jobs, n, nch, sv, tiles, opt.rate);
   if (opt.rate && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_rate: internal: not a plain call in sequence");
   unsigned char* w = static_cast<unsigned char*>(ws);
   SpxStreamDev* dstreams = reinterpret_cast<SpxStreamDev*>(w + L.off_streams);
@@ -622,7 +608,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   const bool ahead_gate = ahead && !force && plan->ahead_started != nullptr && plan->ahead_n > 0 && !waited_prev &&
                           ring_previous_in_flight(plan);
   // (a rate call is never concurrent: the tile order's place in the staging kernel carries its SpxRateJob records instead)
-  rc = stage_tables(plan, sv, opt.rate ? opt.rate->table : order, dstreams, opt.rate ? reinterpret_cast<int*>(opt.rate->d_table) : d_order, d_flags, concurrent ? (unsigned)tiles[0] : 0u, d_ready,
+  const int rc = stage_tables(plan, sv, opt.rate ? opt.rate->table : order, dstreams, opt.rate ? reinterpret_cast<int*>(opt.rate->d_table) : d_order, d_flags, concurrent ? (unsigned)tiles[0] : 0u, d_ready,
                     (concurrent || ahead) ? (unsigned)n + 1u : 0u, (ahead || chunk_ahead) ? sa : st, &staged_ev,
                     ahead_gate ? plan->ahead_started : nullptr, plan->ahead_n, 8000u);
   if (rc) return rc;
@@ -778,6 +764,9 @@ static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
     if (!(M.ahead && M.walk2)) P.k = 1;
   }
   if (P.k <= 1) return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, opt);
+  // every sub-batch's table before the first sub-batch is enqueued: a call that is refused has launched nothing
+  for (int i = 0; i < P.k; i++)
+    if (spx_check_jobs(plan, jobs + P.first[i], P.first[i + 1] - P.first[i])) return -1;
   { std::lock_guard<std::mutex> g(plan->mu); if (plan->split_of.size() > 64) plan->split_of.clear(); plan->split_of[ws] = P.k; }
   int64_t rows = 0;
   for (int i = 0; i < P.k; i++) {
@@ -800,7 +789,7 @@ static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
     if (i == P.k - 1) o.done_event = opt.done_event;   // (on hip_stream, which waits for every sub-batch's walk kernel: never detached)
     const int rc = run_impl(plan, jobs + a, m, in, out, n_out + a, static_cast<unsigned char*>(ws) + P.ws_off[i], P.ws_bytes[i],
                             taps ? &t : nullptr, hs, true, true, o);
-    if (rc) return rc;   // (what the earlier sub-batches enqueued is already joined to hip_stream: ring_record)
+    if (rc) return rc;   // (a HIP error; what the earlier sub-batches enqueued is already joined to hip_stream: ring_record)
   }
   return 0;
 }
@@ -813,20 +802,23 @@ int spx_internal_run(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
   return run_split(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, o);
 }
 
-// What a batch call refuses about its job table -- counts and offsets, speed, nonlinear factor, feedback, the sample rate's and the
-// channel count's LDS limits -- WITHOUT the call: spx_batch_run_float (spx_convert.hip) asks before it enqueues its input conversion,
-// so that a call that is refused has launched nothing.  rate_call: at least one rate other than 1 (the general walk kernel's window).
-int spx_internal_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call) {
+// What every batch call asks FIRST about its job table: the rules of spx_jobs.h for every job, then the one rule that needs a
+// kernel's resources -- the walk kernel's LDS window of the batch's shape.  Host arithmetic only: -1 with spx_last_error, and nothing
+// of the plan's state has changed; 0 and the call can fail on a HIP error only.
+// rate_call: at least one rate other than 1 (the general walk kernel's window); short_window: SpxForce::no_exclusive.
+SpxJobLimits spx_job_limits(spx_plan_t plan) { return {plan->dev.W, plan->dev.B, spx_internal_analysis_fits(plan->dev)}; }
+int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call, bool short_window) {
   if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
-  SpxPlanDev d = plan->dev;
-  if (d.tile_frames < 1) d.tile_frames = spx_analysis_small_tile_frames();
-  std::vector<SpxStreamDev> sv;
-  std::vector<int> tiles;
-  if (build_streams(d, jobs, n, 1, sv, tiles)) return -1;
+  const SpxJobLimits L = spx_job_limits(plan);
+  for (int i = 0; i < n; i++) {
+    const SpxJobFault f = spx_check_job(L, jobs[i]);
+    if (f != SPX_JOB_OK) return fail(-1, std::string("spx_batch: ") + spx_job_fault_text(f));
+  }
   const SpxSpeedClass SC = speed_class(jobs, n);
   std::lock_guard<std::mutex> plan_lock(plan->mu);
-  const SpxModeResources& R = mode_resources(plan, n, SC.maxC, SC.speedup_only && !rate_call, SC.any_speed && !rate_call);
-  if (R.walk.lds > 160 * 1024) return fail(-1, "spx_batch: too many channels for the walk kernel's LDS window");
+  const SpxModeResources& R = mode_resources(plan, n, SC.maxC, SC.speedup_only && !rate_call, SC.any_speed && !rate_call, short_window);
+  if (R.walk.lds > 160 * 1024)   // one CU's LDS; the window holds every channel of maxRequired + 64 frames at least
+    return fail(-1, "spx_batch: too many channels for the walk kernel's LDS window");
   return 0;
 }
 
@@ -882,8 +874,9 @@ static int64_t rate_frames(int64_t m, int old_rate, int new_rate) {
   return m >= 2 ? ((m - 1) * (int64_t)new_rate + old_rate - 1) / old_rate : 0;
 }
 // Workspace of a rate call: the plain call's | SpxRateJob[n] | the walk kernel's counts | the TSM buffers of the jobs with rate != 1
+// (of jobs that have passed spx_check_jobs: spx_internal_out_bound is given no speed that nobody has looked at)
 struct RateLayout { size_t off_table, off_tsm_n, off_tsm, total; std::vector<int64_t> tsm_off, tsm_cap; };
-static int rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, RateLayout& RL) {
+static void rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, RateLayout& RL) {
   size_t o = (spx_batch_workspace_bytes(plan, jobs, n) + 255) & ~(size_t)255;
   RL.off_table = o; o += (sizeof(SpxRateJob) * (size_t)n + 255) & ~(size_t)255;
   RL.off_tsm_n = o; o += (sizeof(int64_t) * (size_t)n + 255) & ~(size_t)255;
@@ -892,17 +885,18 @@ static int rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float*
   int64_t v = 0;
   for (int i = 0; i < n; i++) {
     if (rates[i] == 1.0f) continue;
-    if (jobs[i].channels < 1 || jobs[i].n_in < 0) return fail(-1, "spx_batch: bad job (channels < 1 or a negative count / offset)");
     RL.tsm_off[i] = v;
     RL.tsm_cap[i] = spx_internal_out_bound(plan->dev, jobs[i].n_in, jobs[i].speed, jobs[i].nonlinear != 0.0f);
     v += (RL.tsm_cap[i] * jobs[i].channels + 7) & ~(int64_t)7;   // (every stream's buffer starts on a 16-byte boundary)
   }
   RL.total = o + sizeof(int16_t) * (size_t)v + 128;
-  return 0;
 }
 extern "C" {
 int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate) {
   if (!plan) { fail(-1, "spx_plan_out_capacity_rate: bad arguments"); return -1; }
+  // (the value rules alone: one channel always fits the walk kernel's window)
+  const SpxJobFault f = spx_check_job(spx_job_limits(plan), {0, n_in, 0, 0, 1, speed, nonlinear, 0.0f});
+  if (f != SPX_JOB_OK) return fail(-1, std::string("spx_batch: ") + spx_job_fault_text(f));
   const int64_t cap = spx_internal_out_bound(plan->dev, n_in, speed, nonlinear != 0.0f);
   if (rate == 1.0f) return cap;
   int o = 1, w = 1;
@@ -911,10 +905,12 @@ int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, f
 }
 size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams) {
   if (!rates) return spx_batch_workspace_bytes(plan, jobs, n_streams);
-  if (!plan || !jobs || n_streams < 1) return 0;
-  for (int i = 0; i < n_streams; i++) { int o, w; if (rate_ratio(plan->dev.rate, rates[i], &o, &w)) return 0; }
+  if (!plan || !jobs || n_streams < 1) { fail(-1, "spx_batch: bad arguments"); return 0; }
+  bool any = false;
+  for (int i = 0; i < n_streams; i++) { int o, w; if (rate_ratio(plan->dev.rate, rates[i], &o, &w)) return 0; any = any || rates[i] != 1.0f; }
+  if (spx_check_jobs(plan, jobs, n_streams, any)) return 0;
   RateLayout RL;
-  if (rate_layout(plan, jobs, rates, n_streams, RL)) return 0;
+  rate_layout(plan, jobs, rates, n_streams, RL);
   return RL.total;
 }
 int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
@@ -929,8 +925,9 @@ int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float*
     }
   if (!any) return spx_batch_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs);
   if (!in || !out || !n_out || !ws || (reinterpret_cast<uintptr_t>(out) & 1)) return fail(-1, "spx_batch_run_rate: bad arguments");
+  if (spx_check_jobs(plan, jobs, n, true)) return -1;
   RateLayout RL;
-  if (rate_layout(plan, jobs, rates, n, RL)) return -1;
+  rate_layout(plan, jobs, rates, n, RL);
   if (ws_bytes < RL.total) return fail(-1, "spx_batch_run_rate: workspace too small (spx_batch_workspace_bytes_rate)");
   unsigned char* w = static_cast<unsigned char*>(ws);
   SpxRateCall RC;

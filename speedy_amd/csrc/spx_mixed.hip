@@ -84,6 +84,9 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
   std::vector<std::vector<int>> gi;
   int rc = mixed_groups(n_plans, jobs, plan_index, n, gj, gi);
   if (rc) return rc;
+  // every group's table before anything is enqueued (the device guard, the ring's note, the fork): past this a group fails on a HIP error only
+  for (int g = 0; g < n_plans; g++)
+    if (!gj[g].empty() && spx_check_jobs(plans[g], gj[g].data(), (int)gj[g].size())) return -1;
   const MixedLayout M = mixed_layout(plans, n_plans, gj, n);
   if (!ws || ws_bytes < M.total) return fail(-1, "spx_batch_run_mixed: workspace too small");
   hipStream_t st = static_cast<hipStream_t>(hs);
@@ -101,7 +104,6 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     SpxModeGroup mg;
     mg.n = (int)gj[g].size();
     mg.walk = mode_walk(d, {.n_streams = mg.n, .max_channels = maxC, .speedup_only = SC.speedup_only, .any_speed = SC.any_speed});
-    if (mg.walk.lds > 160 * 1024) return fail(-1, "spx_batch_run_mixed: too many channels for the walk kernel's LDS window");
     mg.any_nonlinear = any_nl;
     mg.an_lds = spx_analysis_lds_bytes(d);
     mg.an_vgprs = spx_analysis_vgprs(d);
@@ -270,8 +272,8 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     go.force = &f;
     rc = run_impl(p, gj[g].data(), (int)gj[g].size(), in, out, d_nout + gpos[g], w + M.ws_off[g], M.ws_bytes[g], taps ? &gtaps[g] : nullptr, gs,
                   true, true, go);
-    // (also when the group failed: whatever it -- and the groups before it -- enqueued on their streams still reads the
-    // caller's buffers, so the caller's stream waits for it before the error is returned)
+    // (also when the group failed -- a HIP error: its table passed spx_check_jobs above --: whatever it and the groups before it
+    // enqueued on their streams still reads the caller's buffers, so the caller's stream waits for it before the error is returned)
     const std::string err = rc ? g_spx_err : std::string();
     hipStream_t join_to = walk2 ? end_stream : st;
     if (gs != join_to && (hipEventRecord(p->ev_join, gs) != hipSuccess || hipStreamWaitEvent(join_to, p->ev_join, 0) != hipSuccess)) {

@@ -1,7 +1,9 @@
-// Host-only build of the launch-mode decision (spx_mode.h) for tests/test_mode_table.py: plain g++, no HIP.  The query and the
-// answer are flat arrays of 64-bit integers so that the Python side mirrors them by NAME (the two name lists below are exported).
+// Host-only build of the launch-mode decision (spx_mode.h) for tests/test_mode_table.py and of the job rules (spx_jobs.h) for
+// tests/test_job_rules.py: plain g++, no HIP.  The mode query and its answer are flat arrays of 64-bit integers so that the Python
+// side mirrors them by NAME (the two name lists below are exported).
 #include <string.h>
 
+#include "spx_jobs.h"
 #include "spx_mode.h"
 
 #define SPX_Q_FIELDS(X)                                                                                                         \
@@ -108,5 +110,14 @@ int spx_mode_table_mixed_mode(const long long* groups, int n_groups, int n_total
 int spx_mode_table_mixed_walk2(int concurrent, int ahead, int detached, int taps) {
   SpxMixedMode M = {concurrent != 0, ahead != 0, false, false};
   return spx_mixed_walk2(M, detached != 0, taps != 0) ? 1 : 0;
+}
+// spx_check_job for one job of a plan with window W, frame step B; the SpxJobFault code, and the rule's text for a code
+int spx_mode_table_check_job(int W, int B, int analysis_fits, int channels, long long n_in, long long in_off, long long out_off,
+                             long long out_cap, float speed, float nonlinear, float feedback) {
+  const spx_stream_job j = {in_off, n_in, out_off, out_cap, channels, speed, nonlinear, feedback};
+  return spx_check_job({W, B, analysis_fits != 0}, j);
+}
+const char* spx_mode_table_job_fault_text(int code) {
+  return code < SPX_JOB_OK || code > SPX_JOB_TOO_LONG ? "" : spx_job_fault_text(static_cast<SpxJobFault>(code));
 }
 }

@@ -28,13 +28,14 @@
 // per batch against 1.67 - 1.70.  Not kept.
 #include <string.h>
 
-#include <cmath>
 #include <string>
 #include <vector>
 
 #include "../../include/speedy_hip.h"
 #include "spx_internal.h"
+#include "spx_jobs.h"
 
+SpxJobLimits spx_job_limits(spx_plan_t plan);   // spx_engine.hip
 int spx_internal_run(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out, void* ws,
                      size_t ws_bytes, const spx_taps* taps, void* hs, bool ahead, bool overlap, void* in_ready, void* done_event, bool detached);
 int spx_internal_run_mixed(const spx_plan_t* plans, int n_plans, const spx_stream_job* jobs, const int* plan_index, int n, const int16_t* in,
@@ -167,6 +168,13 @@ static void pipeline_free(spx_pipeline* p) {
   delete p;
 }
 
+static int lane_fail(int lane, const std::string& what) { return pfail(-1, "spx_pipeline: lane " + std::to_string(lane) + ": " + what); }
+// A lane's job by the engine's rules (spx_jobs.h), in the engine's words, with the lane in front
+static int lane_check(const spx_pipeline* p, int lane, const spx_stream_job& j) {
+  const SpxJobFault f = spx_check_job(spx_job_limits(p->plans[p->mixed ? p->plan_index[lane] : 0]), j);
+  return f == SPX_JOB_OK ? 0 : lane_fail(lane, spx_job_fault_text(f));
+}
+
 static int pipeline_build(spx_pipeline* p) {
   const int n = p->n;
   PCHK(hipGetDevice(&p->device));
@@ -178,7 +186,8 @@ static int pipeline_build(spx_pipeline* p) {
   p->static_offsets.resize((size_t)n + 1);
   for (int i = 0; i < n; i++) {
     spx_stream_job& j = p->jobs[i];
-    if (j.channels < 1 || j.n_in < 0 || j.in_off < 0) return pfail(-1, "spx_pipeline: bad job (channels < 1 or a negative count / offset)");
+    j.out_off = j.out_cap = 0;   // (the caller's are not read: the pipeline lays its own output out below)
+    if (lane_check(p, i, j)) return -1;
     spx_plan_t pl = p->plans[p->mixed ? p->plan_index[i] : 0];
     j.out_cap = spx_plan_out_capacity_for(pl, j.n_in, j.speed, j.nonlinear);
     j.out_off = oo;
@@ -337,14 +346,11 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, siz
   return ticket;
 }
 
-static int lane_fail(int lane, const std::string& what) { return pfail(-1, "spx_pipeline: lane " + std::to_string(lane) + ": " + what); }
-
 // Does the caller's table fit the pipeline?  0 with `table` = the caller's jobs in the pipeline's own output layout and `extent` =
 // the int16 values of input the batch reads, or -1 with the lane and the limit in spx_last_error.  Host arithmetic only.
 // The limits are the pipeline's own: the lane's channel count, the input buffer, the lane's output capacity, the workspace.
-// A job's VALUES are the engine's to judge (build_streams, spx_engine.hip) -- but the engine judges inside a call, behind the wait
-// for the buffer set and the copy in, and a refusal here has to come before both: the rules on speed, nonlinear factor, feedback
-// strength and length are therefore asked here first, in the engine's words; the call itself still applies every rule it has.
+// A job's VALUES are judged by the engine's rules (lane_check: spx_jobs.h, the rules every batch call applies at its top), asked
+// here per lane so that the message names the lane and comes before the wait for the buffer set and the copy in.
 static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, std::vector<spx_stream_job>& table, size_t* extent) {
   const int n = p->n;
   table.assign(jobs, jobs + n);
@@ -354,11 +360,9 @@ static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, std::vec
     const spx_stream_job& c = p->jobs[i];
     if (j.channels != c.channels)
       return lane_fail(i, std::to_string(j.channels) + " channels, the lane was created with " + std::to_string(c.channels));
-    if (j.n_in < 0 || j.in_off < 0) return lane_fail(i, "bad job (a negative count / offset)");
-    if (!(j.speed > 0.0f) || !std::isfinite(j.speed)) return lane_fail(i, "speed must be finite and > 0");
-    if (!(j.nonlinear >= 0.0f && j.nonlinear <= 1.0f)) return lane_fail(i, "nonlinear factor outside [0, 1]");
-    if (!std::isfinite(j.feedback)) return lane_fail(i, "feedback strength is not finite");
-    if (j.n_in >= (1ll << 30)) return lane_fail(i, "stream of 2^30 frames or more");
+    j.out_off = c.out_off;
+    j.out_cap = c.out_cap;
+    if (lane_check(p, i, j)) return -1;
     if ((uint64_t)j.in_off > p->in_values || (uint64_t)j.n_in * (uint64_t)j.channels > p->in_values - (uint64_t)j.in_off)
       return lane_fail(i, "in_off " + std::to_string(j.in_off) + " + n_in " + std::to_string(j.n_in) + " x " + std::to_string(j.channels) +
                               " channels ends behind the pipeline's input of " + std::to_string(p->in_values) + " values (spx_pipeline_input_values)");
@@ -369,8 +373,6 @@ static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, std::vec
       return lane_fail(i, "n_in " + std::to_string(j.n_in) + " at speed " + std::to_string(j.speed) + (j.nonlinear != 0.0f ? " nonlinear" : " linear") +
                               " needs an output capacity of " + std::to_string(need) + " frames (spx_plan_out_capacity_for), the lane was created with " +
                               std::to_string(c.out_cap));
-    j.out_off = c.out_off;
-    j.out_cap = c.out_cap;
   }
   const size_t ws = p->mixed ? spx_batch_workspace_bytes_mixed(p->plans.data(), (int)p->plans.size(), table.data(), p->plan_index.data(), n)
                              : spx_batch_workspace_bytes(p->plans[0], table.data(), n);

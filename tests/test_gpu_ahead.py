@@ -498,6 +498,49 @@ def test_step_counts_after_a_split_call_then_the_two_halves_on_the_same_workspac
     assert list(b.step_counts()) == want_steps and _crc(b.results()) == want_crc
 
 
+def test_a_refused_call_of_more_streams_than_cus_launches_nothing(orc):
+    """An overlapped call of more streams than the device has CUs is cut into sub-batches that are enqueued one after the other: a
+    bad LAST job must be found before the first sub-batch is enqueued.  A feedback strength of NaN or a negative capacity leaves the
+    decision to split as it is (it reads speeds, nonlinear factors and channel counts only); a speed of 0 makes the same table one
+    call.  Then the valid table on the same objects: it WAS split, and three streams against the oracle.
+    (No call is split in a process in which spx_set_pipeline_chunks was ever called -- run_split; this file runs before those that do.)"""
+    import ctypes as C
+    import torch
+    from util import refused_and_untouched
+    from speedy_amd.batch import Batch, Plan
+    from speedy_amd.synth import speech_like
+    rate = 16000
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = cus + 2
+    base = speech_like(2000 + n, rate, seed=31)
+    streams = [base[i:i + 2000] for i in range(n)]
+    plan = Plan(rate, False)
+    try:
+        b = Batch(plan, [2000] * n, 1, 3.5, 1.0, 0.0)
+        b.upload(streams)
+        L = plan.L
+        hs = torch.cuda.current_stream().cuda_stream
+        last = b.jobs[n - 1]
+        for field, value, word in (("feedback", float("nan"), "feedback"), ("out_cap", -1, "bad job"), ("speed", 0.0, "speed")):
+            good = getattr(last, field)
+            setattr(last, field, value)
+            refused_and_untouched(b, L, lambda: L.spx_batch_run_overlapped(
+                plan.h, b.jobs, b.n, b.d_in.data_ptr(), b.d_out.data_ptr(), b.d_nout.data_ptr(), b.d_ws.data_ptr(), b.d_ws.numel(), None, hs),
+                word)
+            setattr(last, field, good)
+        b.run_ahead(overlap=True)
+        res = b.results()
+        for i in (0, n // 2, n - 1):
+            assert np.array_equal(res[i], orc.compress_sound(streams[i], rate, 1, 3.5, 1.0, 0.0, False, chunk=1000)["out"]), i
+        # the call was cut in two: the plan remembers that for the workspace, and spx_batch_read_steps refuses a table that is not cut alike
+        steps = (C.c_int32 * n)()
+        assert L.spx_batch_read_steps(plan.h, b.jobs, cus, b.d_ws.data_ptr(), steps, hs) == -1
+        assert b"not those of the call" in L.spx_last_error(), L.spx_last_error()
+        assert (b.step_counts() > 0).all()
+    finally:
+        plan.close()
+
+
 def test_large_calls_pipelined_producers_ahead(orc):
     """Round 6: a pipelined call of more than two streams per CU (time chunks, throughput-form walk kernels) starts its producers at
     once on the side stream -- the next call's first analysis chunk beside this call's last walk chunk.  600 ragged streams per call,

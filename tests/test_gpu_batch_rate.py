@@ -297,6 +297,19 @@ def test_bad_rates_are_refused_before_anything_is_launched():
             assert bool((b.d_out == CANARY).all()) and bool((b.d_nout == -77).all()), "rate %r: a refused call wrote its buffers" % bad
             assert L.spx_batch_workspace_bytes_rate(plan.h, b.jobs, b._rates_ptr(), b.n) == 0
             assert L.spx_plan_out_capacity_rate(plan.h, 16000, 3.5, 1.0, bad) == -1
+        # ... and a good rate on a job whose SPEED is refused: the message names the speed (nobody sizes a buffer from it first)
+        b.rates = np.ascontiguousarray(np.full(b.n, 1.25, np.float32))
+        b.jobs[3].speed = float("nan")
+        b.d_out.fill_(CANARY)
+        b.d_nout.fill_(-77)
+        rc = L.spx_batch_run_rate(plan.h, b.jobs, b._rates_ptr(), b.n, b.d_in.data_ptr(), b.d_out.data_ptr(), b.d_nout.data_ptr(),
+                                  b.d_ws.data_ptr(), b.d_ws.numel(), None, torch.cuda.current_stream().cuda_stream)
+        assert rc == -1 and "speed" in L.spx_last_error().decode(), L.spx_last_error()
+        torch.cuda.synchronize()
+        assert bool((b.d_out == CANARY).all()) and bool((b.d_nout == -77).all()), "speed NaN: a refused call wrote its buffers"
+        assert L.spx_batch_workspace_bytes_rate(plan.h, b.jobs, b._rates_ptr(), b.n) == 0
+        assert "speed" in L.spx_last_error().decode()
+        assert L.spx_plan_out_capacity_rate(plan.h, 16000, float("nan"), 0.0, 1.25) == -1
     finally:
         plan.close()
 

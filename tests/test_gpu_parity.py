@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from util import read_wav
+from util import CANARY, read_wav, refused_and_untouched
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -577,6 +577,41 @@ def test_jobs_outside_the_defined_ranges_are_refused():
     b.jobs[0].channels = 400
     with pytest.raises(RuntimeError):
         b.run()
+
+
+@pytest.mark.parametrize("bad_group", [1, 0])
+def test_a_refused_mixed_call_launches_nothing(orc, bad_group):
+    """Two plans with three jobs each; one job of a group has a feedback strength of NaN.  The groups are enqueued one after the
+    other (16 kHz first): the bad job must be found before ANY group is -- spx_batch_run_mixed and spx_batch_run_mixed_ahead.
+    Then the valid table on the same objects, every job against the oracle."""
+    import torch
+    from speedy_amd.batch import MixedBatch, Plan
+    from speedy_amd.synth import speech_like
+    rates = [16000, 22050]
+    plans = [Plan(r, False) for r in rates]
+    try:
+        pidx = [0, 1, 0, 1, 0, 1]
+        xs = [speech_like(2000, rates[g], seed=40 + i) for i, g in enumerate(pidx)]
+        b = MixedBatch(plans, pidx, [2000] * 6, 1, 3.5, 1.0, 0.0)
+        b.upload(xs)
+        L = b.L
+        hs = torch.cuda.current_stream().cuda_stream
+        args = (b.hplans, len(plans), b.jobs, b.plan_index, b.n, b.d_in.data_ptr(), b.d_out.data_ptr(), b.d_nout.data_ptr(),
+                b.d_ws.data_ptr(), b.d_ws.numel(), hs)
+        bad = pidx.index(bad_group, 2)   # the group's second job
+        b.jobs[bad].feedback = float("nan")
+        refused_and_untouched(b, L, lambda: L.spx_batch_run_mixed(*args), "feedback")
+        refused_and_untouched(b, L, lambda: L.spx_batch_run_mixed_ahead(*args), "feedback")
+        b.jobs[bad].feedback = 0.0
+        want = [_oracle(orc, xs[i], rates[g], 1, 3.5, 1.0, 0.0, False)["out"] for i, g in enumerate(pidx)]
+        for run in (b.run, b.run_ahead):
+            b.d_out.fill_(CANARY)
+            run()
+            for i, got in enumerate(b.results()):
+                assert np.array_equal(got, want[i]), (run.__name__, i)
+    finally:
+        for p in plans:
+            p.close()
 
 
 @pytest.mark.parametrize("rate,ch", [(16000, 64), (22050, 40), (22050, 64), (44100, 40), (8000, 100), (48000, 24)])

@@ -325,6 +325,17 @@ def test_refused_arguments_edge_shapes_and_destroy_in_flight(orc):
         Pipeline([plan], [8000] * 2, 1, 3.0, 1.0, 0.0, plan_index=[0, 1])
     with pytest.raises(RuntimeError):
         Pipeline(plan, [8000, 8000], [1, 0], 3.0, 1.0, 0.0)       # channels < 1
+    # a creation table that breaks one of the engine's value rules is refused at creation, lane and rule named -- not at every submit
+    for speed, fb, word in (([3.0, 0.0], 0.0, "speed"), (3.0, [0.0, float("nan")], "feedback")):
+        with pytest.raises(RuntimeError) as e:
+            Pipeline(plan, [8000, 8000], 1, speed, 1.0, fb)
+        assert L.spx_last_error() and "lane 1" in str(e.value) and word in str(e.value), str(e.value)
+    # ... and the plan serves a pipeline created right after
+    x = speech_like(8000, rate, seed=1099)
+    pipe = Pipeline(plan, [8000, 8000], 1, 3.0, 1.0, 0.0)
+    got = pipe.results(pipe.submit(pipe.pack([x, x])))[1]
+    assert np.array_equal(got, orc.compress_sound(x, rate, 1, 3.0, 1.0, 0.0, False, chunk=1000, taps=False)["out"])
+    pipe.close()
     # edge shapes
     cases = [([24000], [3.0], [1.0]),                                  # one stream
              ([24000, 0, 100, 239, 16000, 1], [3.0, 2.0, 3.5, 2.5, 1.5, 2.0], [1.0, 1.0, 1.0, 1.0, 1.0, 1.0]),   # empty / shorter than a window

@@ -28,3 +28,19 @@ def read_wav(name):
 
 def matlab_fixture():
     return np.load(os.path.join(GOLDEN, "tapestry22050_matlab.npz"))
+
+
+CANARY = 0x5a5a   # an int16 pattern no kernel writes on purpose
+
+
+def refused_and_untouched(b, L, call, word):
+    """`call` (the C entry point on b's buffers) returns -1 with `word` in the message, and out / n_out keep their canaries."""
+    import torch
+    b.d_out.fill_(CANARY)
+    b.d_nout.fill_(-77)
+    rc = call()
+    msg = L.spx_last_error().decode()
+    torch.cuda.synchronize()
+    assert rc == -1 and word in msg, (rc, msg)
+    assert bool((b.d_nout == -77).all()), "a refused call wrote n_out"
+    assert bool((b.d_out == CANARY).all()), "a refused call wrote out"
