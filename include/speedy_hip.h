@@ -340,11 +340,16 @@ int spx_debug_last_walk_form(void);
 int spx_debug_kernel_vgprs(int which);
 /* Diagnostics: the walk kernel a batch of this shape would be served by -- out[0] allocated VGPRs, out[1] scratch bytes per lane
  * (spilled registers), out[2] LDS bytes per workgroup, out[3] its form (as spx_debug_last_walk_form), out[4] waves per workgroup --
- * and the analysis kernel of a sample rate (out[0 .. 2] alike; out[3] the waves that transform frames: 4, 2 or 1).
+ * and the analysis kernel of a sample rate (out[0 .. 2] alike, out[2] for a launch whose streams are all mono; out[3] the waves
+ * that transform frames: 4, 2 or 1).
  * tests/test_gpu_parity.py pins these per (rate, channels, batch size): the engine's choice of launch mode is arithmetic
  * over them. */
 int spx_debug_walk_info(int sample_rate, int channels, int n_streams, int speedup_only, int short_jobs, int lean, int* out5);
 int spx_debug_analysis_info(int sample_rate, int* out4);
+/* Diagnostics, host code only (no GPU needed): the lane-major constant table of the 16 kHz analysis kernel as a plan of this
+ * sample rate holds it (15 entries x 64 lanes x 16 bytes into out) and the tables it is filled from (tw, tw2: 480 doubles each,
+ * win: 240 floats).  Returns the table's size in bytes, 0 for a rate whose window is not 240 samples, -1 on a null pointer. */
+int spx_debug_lane_consts(int sample_rate, void* out, double* tw, double* tw2, float* win);
 /* Diagnostics: the 22 resource numbers the engine's launch-mode decision (speedy_amd/csrc/spx_mode.h, a pure function) is fed for a
  * batch of this shape: CUs, LDS per CU, the walk kernel's form as picked and in its lean form (LDS, waves, VGPRs, fast kernel?, output
  * waves; lean form exists?), the tension kernel's LDS and VGPRs, the analysis tiles (the plan's, 16, 8 frames) and the analysis

@@ -88,6 +88,7 @@ SYMBOLS = {
     "spx_debug_log_check": (C.c_int, [C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong)]),
     "spx_debug_walk_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "spx_debug_analysis_info": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    "spx_debug_lane_consts": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), c_float_p]),
     "spx_debug_mode_resources": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
     "spx_pipeline_create": (C.c_void_p, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_int, C.c_uint]),
     "spx_pipeline_create_mixed": (C.c_void_p, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(StreamJob), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_uint]),

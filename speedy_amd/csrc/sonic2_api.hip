@@ -461,7 +461,7 @@ static int launch_job(sonicStream s, bool flush, bool direct = false) {
     td.features = s->tFeatures.base() - fo * SPX_FEATURE_COUNT;
     td.spectrogram = s->tSpec.base() - fo * P.N; td.normalized = s->tNorm.base() - fo * P.W;
   }
-  if (J.tiles > 0) spx_launch_analysis(P, s->dJob, 1, J.tiles, s->dIn.p, s->dRec.p, td, nullptr, nullptr, s->hs);
+  if (J.tiles > 0) spx_launch_analysis(P, s->dJob, 1, J.tiles, s->dIn.p, s->dRec.p, td, nullptr, nullptr, C == 1, s->hs);
   if (J.nonlinear) spx_launch_tension(P, s->dJob, 1, s->dState, s->dRec.p, s->dScr.p, td, nullptr, nullptr, s->hs);
   // short_jobs: one write, a few pitch steps -- the usual window, not the long one
   spx_launch_walk(P, {.n_streams = 1, .max_channels = (int)C, .speedup_only = J.speedupKernel, .short_jobs = true}, dJobW, J.tsmIn->p,

@@ -577,7 +577,7 @@ static RunLaunch launch_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
   for (const Group& g : groups) {
     const SpxPlanDev& PL = *items[g.i0].s->plan;
     const int ng = (int)(g.i1 - g.i0);
-    if (g.tiles > 0) spx_launch_analysis(PL, dA + g.i0, ng, g.tiles, nullptr, P->aRec, no_taps, nullptr, nullptr, P->hs);
+    if (g.tiles > 0) spx_launch_analysis(PL, dA + g.i0, ng, g.tiles, nullptr, P->aRec, no_taps, nullptr, nullptr, /*mono=*/false, P->hs);
     lap(1);
     bool any_nl = false;
     for (size_t i = g.i0; i < g.i1; i++) any_nl = any_nl || items[i].J.nonlinear;

@@ -111,15 +111,31 @@ int spx_analysis_prefers_small_tile(const SpxPlanDev& P) {  // plan creation: wi
 static __host__ __device__ inline size_t stage_samples(const SpxPlanDev& P, int tf) {
   return (size_t)(tf + 1) * P.B + (P.W - P.B) + 8;  // mono samples of frames j0-1 .. j0+TF-1
 }
-static size_t analysis_lds_bytes(const SpxPlanDev& P, bool ct) {  // for the tile size the plan copy carries (P.tile_frames)
+// The 16-frame instantiation of W = 240 (16 kHz: the pipelined headline shape) is laid out for THREE workgroups per CU beside two
+// lean walk workgroups -- 2 x 29 + 3 x 22 of the CU's 128 LDS granules of 1280 bytes:
+//   [ magnitude rows 0 .. 12 | work area | staged span (launches with a multi-channel stream only) ]
+// Rows 13 .. 16 -- each the LAST slot of one of the four waves -- lie over the head of the work area (wave 0's transform buffer and
+// 64 bytes of wave 1's), contiguous with the rows in front: a wave keeps its last row in registers until the tile's transforms are
+// done (one more workgroup barrier) and stores it then.  The three small arrays, the blocks of log terms and the log table follow
+// in the work area, which only the transforms need whole.
+static __host__ __device__ constexpr bool an_lean_layout(int tf, int wct) { return tf == SPX_TF && wct == 240; }
+#define SPX_LT_FRONT_ROWS 13
+static __host__ __device__ constexpr size_t an_lt_front_bytes() { return (size_t)SPX_LT_FRONT_ROWS * spx_mag_stride(240) * sizeof(float); }
+static __host__ __device__ constexpr size_t an_lt_small_off() { return (size_t)(SPX_TF + 1 - SPX_LT_FRONT_ROWS) * spx_mag_stride(240) * sizeof(float); }
+static __host__ __device__ constexpr size_t an_lt_terms_off() { return (an_lt_small_off() + 3 * (SPX_TF + 1) * sizeof(float) + 15) & ~(size_t)15; }
+static_assert(SPX_TF + 1 - SPX_LT_FRONT_ROWS == 4, "one held row per wave");
+static_assert(an_lt_front_bytes() % 16 == 0 && an_lt_small_off() % 16 == 0, "16-byte rows, 16-byte work area");
+static size_t analysis_lds_bytes(const SpxPlanDev& P, int ctw, bool mono) {  // for the tile size the plan copy carries (P.tile_frames)
   const int tf = P.tile_frames > 0 ? P.tile_frames : SPX_TF;
+  const bool ct = ctw != 0;
   size_t mags = (size_t)(tf + 1) * spx_mag_stride(P.W) * sizeof(float);
   size_t small = (size_t)3 * (tf + 1) * sizeof(float);
   size_t stage = (stage_samples(P, tf) * sizeof(short) + 15) & ~(size_t)15;
+  if (an_lean_layout(tf, ctw)) return an_lt_front_bytes() + work_bytes(P.W, tf, ct, P.dft_waves) + (mono ? 0 : stage);
   return work_bytes(P.W, tf, ct, P.dft_waves) + ((mags + 15) & ~(size_t)15) + ((small + 15) & ~(size_t)15) + stage;
 }
 // what spx_launch_analysis (int16 input) will ask for: the engine's co-residency arithmetic uses this
-size_t spx_analysis_lds_bytes(const SpxPlanDev& P) { return analysis_lds_bytes(P, plan_ct_window(P) != 0); }
+size_t spx_analysis_lds_bytes(const SpxPlanDev& P, bool mono) { return analysis_lds_bytes(P, plan_ct_window(P), mono); }
 int spx_analysis_ct_window(const SpxPlanDev& P) { return plan_ct_window(P); }   // which instantiation serves the plan (0 = plan-driven)
 
 __device__ __forceinline__ void wave_sync() {
@@ -491,14 +507,12 @@ __device__ __forceinline__ double uniform_f64(double v) {  // a wave-uniform dou
 // 44 -> 26 instructions for the four samples of a lane in the 16 kHz kernel.  Bit-identical, the spec (oracle) is untouched.
 // md, mpd: (double)m, (double)mp.  -DSPX_PREEMPH_V1: the literal sequence.
 #ifdef SPX_PREEMPH_V1
-#define SPX_WIN_SCALE 1.0f
 __device__ __forceinline__ float spx_preemph_win_f32(double md, double mpd, float w) {
   const float x = (float)(md / 32768.0), xp = (float)(mpd / 32768.0);
   const float y = (float)(1.0 * (double)x - 0.97 * (double)xp);
   return y * w;
 }
 #else
-#define SPX_WIN_SCALE 0x1p-15f
 __device__ __forceinline__ float spx_preemph_win_f32(double md, double mpd, float w15) {
   const float yy = (float)(md - 0.97 * mpd);
   return yy * w15;
@@ -521,7 +535,7 @@ __device__ __forceinline__ cplx packed_point(const short* fr, int n, int j, int 
 #define SPX_AN_W_BIG 2   // waves per SIMD the 44.1 / 48 kHz instantiations are compiled for (A/B: 3 = 168 registers)
 #endif
 template <int TF, int WCT>
-__global__ void __launch_bounds__(SPX_BLOCK, (WCT == 240 || WCT == 120 || WCT == 180) ? 4 : WCT == 330 ? SPX_AN_W_330 : (WCT == 661 || WCT == 720) ? SPX_AN_W_BIG : (WCT == 480 || WCT == 360) ? 2 : 1)  // (.., waves per SIMD the register count must allow: the concurrent mode's budgets)
+__global__ void __launch_bounds__(SPX_BLOCK, an_lean_layout(TF, WCT) ? 5 : (WCT == 240 || WCT == 120 || WCT == 180) ? 4 : WCT == 330 ? SPX_AN_W_330 : (WCT == 661 || WCT == 720) ? SPX_AN_W_BIG : (WCT == 480 || WCT == 360) ? 2 : 1)  // (.., waves per SIMD the register count must allow: the concurrent mode's budgets)
 spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int n_streams,
                     const int16_t* __restrict__ in_base, SpxFrameRec* __restrict__ rec, SpxTapsDev taps,
                     const int* __restrict__ tile_order, int* tile_flags, const float* __restrict__ frames,
@@ -546,19 +560,26 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
   const int C = S.channels;
   const int16_t* __restrict__ in = in_base + S.in_off;
 
-  double* work = reinterpret_cast<double*>(lds);
+  constexpr bool LT = an_lean_layout(TF, WCT);   // (see an_lean_layout: magnitude rows in front, the last four over the work area)
   const size_t wb = work_bytes(W, TF, WCT != 0, (WCT != 0) ? 4 : P.dft_waves);
-  float* mags = reinterpret_cast<float*>(lds + wb);
   const size_t mags_b = (((size_t)(TF + 1) * spx_mag_stride(W) * sizeof(float)) + 15) & ~(size_t)15;
-  float* fE = reinterpret_cast<float*>(lds + wb + mags_b);
+  const size_t small_b = (((size_t)3 * (TF + 1) * sizeof(float)) + 15) & ~(size_t)15;
+  double* work = reinterpret_cast<double*>(LT ? lds + an_lt_front_bytes() : lds);
+  float* mags = reinterpret_cast<float*>(LT ? lds : lds + wb);
+  float* fE = reinterpret_cast<float*>(LT ? lds + an_lt_front_bytes() + an_lt_small_off() : lds + wb + mags_b);
   float* fThr = fE + (TF + 1);
   float* fInv = fThr + (TF + 1);
   const int MS = spx_mag_stride(W);  // mags row stride (floats)
+  // the blocks of log terms and, behind them, the log table: in the work area, at its start unless magnitude rows lie there
+  unsigned char* const terms_base = reinterpret_cast<unsigned char*>(work) + (LT ? an_lt_terms_off() : 0);
+  static_assert(!LT || an_lt_terms_off() + (size_t)2 * SPX_TF * (spx_cb(SPX_TF) + 1) * sizeof(double) + SPX_LOG_LDS_BYTES <= (size_t)4 * 2 * 240 * sizeof(double),
+                "two blocks of log terms and the log table inside the work area (terms_bytes, work_bytes)");
 
-  const size_t small_b = (((size_t)3 * (TF + 1) * sizeof(float)) + 15) & ~(size_t)15;
   const double* ltw = P.tw;    // twiddles stay in global memory (L1-resident, 16 B per lane per use)
   const double* ltw2 = P.tw2;
-  short* smono = reinterpret_cast<short*>(lds + wb + mags_b + small_b);    // mono mix of the tile's input span
+  short* smono = reinterpret_cast<short*>(LT ? lds + an_lt_front_bytes() + wb : lds + wb + mags_b + small_b);    // mono mix of the tile's input span
+  // frame_mode 3 (int16 launches of the lean layout whose streams are all mono): no staged span, stage 1 reads global memory
+  const bool direct = LT && frame_mode == 3;
 
   double* bufA = work + (size_t)wave * (WCT != 0 ? 2 : 4) * W;
   double* bufB = (WCT != 0) ? bufA : bufA + 2 * W;  // compiled-in sizes: one buffer per wave, every stage in place
@@ -567,8 +588,8 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
   const int jfirst = (j0 > 0) ? j0 - 1 : 0;            // first frame whose samples are needed
   const int64_t sbase = (int64_t)jfirst * B;           // absolute index of smono[0]
   const int nstage = (j1 - jfirst) * B + (W - B);      // frames jfirst .. j1-1
-  if (frames != nullptr) {
-    // explicit float frames (unit-level API): nothing to stage
+  if (frames != nullptr || direct) {
+    // explicit float frames (unit-level API), or mono samples read where they are: nothing to stage
   } else if (C == 1) {
     const int16_t* __restrict__ src = in + sbase;
     for (int k0 = tid; k0 < nstage; k0 += 8 * SPX_BLOCK) {
@@ -585,7 +606,201 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
 
   ASTAMP_DECL
   // ---------------- phase 1: spectra of slots 0..TF (slot s = frame j0-1+s), one wave per slot ----------
-  if constexpr (WCT == 240) {
+  if constexpr (LT) {
+    // W = 240, sixteen frames: the transform of the branch below (same butterflies, same operations in the same order, in place on
+    // one buffer per wave), built for 88 registers -- three waves of it beside two lean walk waves on a SIMD.  What the branch
+    // below loads once and holds across the tile (sixty registers of twiddles, untangle factors and window values) comes from
+    // the plan's lane-major table (SpxPlanDev::lane_consts: entry [c][lane], L1-resident) group by group, each group right
+    // before the stage that uses it and issued before the previous stage's LDS traffic has drained; the pointer is laundered
+    // once per slot (per_frame) so that nothing is hoisted back out of the loop.  A launch of mono streams reads a slot's six
+    // samples per lane from global memory (`direct`; the next slot's are on their way during the untangle) and has no staged
+    // span.  Each wave's last slot (rows 13 .. 16) stays in four registers until every wave is through its transforms: those
+    // rows lie over wave 0's buffer (an_lean_layout).
+    const int b = lane;
+    const bool on60 = b < 60, on48 = b < 48;
+    const int bb = on60 ? b : 0;
+    // (a global-memory pointer by its type: behind the laundering the compiler no longer sees where it came from and would emit
+    // flat loads.  As generated: one 64-bit add of the lane's offset per scalar base, global loads with immediates from there)
+    typedef double lc_v2d __attribute__((ext_vector_type(2)));
+    typedef float lc_v4f __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) lc_v2d* lc_ptr;
+    typedef const __attribute__((address_space(1))) lc_v4f* lc_ptr4;
+    const double2* const lc0 = reinterpret_cast<const double2*>(P.lane_consts);
+    // the six samples a lane's first butterfly takes of frame j: fr = the frame's sample 2 bb.  m[4] is the sample in front of
+    // m[0] -- for bb = 0 the previous window's last sample, which is sample W - B - 1 of this one (0 in front of frame 0)
+    auto take6 = [&](auto fr, int j, int (&m)[6]) {
+      m[0] = fr[0]; m[1] = fr[1]; m[2] = fr[120]; m[3] = fr[121]; m[5] = fr[119];
+      m[4] = fr[bb > 0 ? -1 : (240 - B) - 1];
+      if (bb == 0 && j == 0) m[4] = 0;
+    };
+    // direct: the samples of slot s, from global memory (a slot without a frame: nothing is read)
+    auto fetch6 = [&](int s, int (&m)[6]) {
+      const int j = j0 - 1 + s;
+      if (s <= TF && j >= 0 && j < j1) take6(in + (int64_t)j * B + 2 * bb, j, m);
+    };
+    int nx[6] = {0, 0, 0, 0, 0, 0};
+    float hold[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (direct) fetch6(wave, nx);
+    for (int s = wave; s <= TF; s += 4) {
+      const int j = j0 - 1 + s;
+      const bool keep = s + 4 > TF;   // the wave's last slot: its row is stored behind the barrier below
+      float* mrow = mags + (size_t)s * MS;
+      if (j < 0 || j >= j1) {  // outside the stream (or the tile's tail): zero spectrum
+        if (!keep) for (int k = lane; k < 240; k += SPX_WAVE) mrow[k] = 0.0f;
+#pragma unroll
+        for (int u = 0; u < 4; u++) hold[u] = 0.0f;
+        if (direct) fetch6(s + 4, nx);
+        continue;
+      }
+      // the lane's number as this slot's own: what derives from it (LDS addresses of every stage, some twenty registers if the
+      // compiler hoists them out of the loop) is computed where it is used
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      __builtin_assume(ln >= 0 && ln < SPX_WAVE);
+      // entry [c][lane]: a scalar base per four entries (an immediate offset reaches 4 KB; each laundered, or the compiler folds
+      // them into lane offsets of their own), plus the lane's offset, plus an immediate
+      const lc_ptr lcb[4] = {(lc_ptr)per_frame(lc0), (lc_ptr)per_frame(lc0 + 256), (lc_ptr)per_frame(lc0 + 512), (lc_ptr)per_frame(lc0 + 768)};
+      typedef const __attribute__((address_space(1))) unsigned char* lc_bytes;
+      unsigned lane_off = 16u * (unsigned)lane;   // (its 32 bits as they are: the load then takes it beside the scalar base)
+      asm volatile("" : "+v"(lane_off));
+      auto lc = [&](int c) -> double2 {
+        const lc_v2d v = *(lc_ptr)((lc_bytes)lcb[c >> 2] + lane_off + 1024u * (unsigned)(c & 3));
+        return make_double2(v.x, v.y);
+      };
+      int m[6];
+      if (direct) {
+#pragma unroll
+        for (int u = 0; u < 6; u++) m[u] = nx[u];
+      } else {
+        take6(smono + (size_t)(j - jfirst) * B + 2 * bb, j, m);
+      }
+      // stage 1 (radix 4, s = 1) on packed points z[n] = v[2n] + i v[2n+1]; v = windowed pre-emphasised samples,
+      // z[n] = 0 for n >= 120: butterfly b (the lane) takes z[b], z[b+60], 0, 0 and writes points 4b .. 4b+3
+      {
+        const lc_v4f wn = *(lc_ptr4)((lc_bytes)lcb[SPX_LC_WN >> 2] + lane_off + 1024u * (SPX_LC_WN & 3));
+        const double2 w1a = lc(SPX_LC_W1 + 0), w1b = lc(SPX_LC_W1 + 1), w1c = lc(SPX_LC_W1 + 2);
+        if (on60) {
+          const double d0 = (double)m[0], d2 = (double)m[2];
+          const cplx a0 = {spx_preemph_win(d0, (double)m[4], wn.x), spx_preemph_win((double)m[1], d0, wn.y)},
+                     a1 = {spx_preemph_win(d2, (double)m[5], wn.z), spx_preemph_win((double)m[3], d2, wn.w)};
+          const cplx b0 = {a0.r + a1.r, a0.i + a1.i}, b2 = {a0.r - a1.r, a0.i - a1.i};
+          const cplx b1 = {a0.r + a1.i, a0.i - a1.r}, b3 = {a0.r - a1.i, a0.i + a1.r};
+          st(bufA, 4 * ln, b0);
+          st(bufA, 4 * ln + 1, cmul_tw(b1, w1a));
+          st(bufA, 4 * ln + 2, cmul_tw(b2, w1b));
+          st(bufA, 4 * ln + 3, cmul_tw(b3, w1c));
+        }
+      }
+      {
+        const double2 w2a = lc(SPX_LC_W2 + 0), w2b = lc(SPX_LC_W2 + 1), w2c = lc(SPX_LC_W2 + 2);   // (stage 2's)
+        wave_sync();
+        ASTAMP(0);
+        // stage 2 (radix 4, s = 4), in place
+        if (on60) {
+          const cplx a0 = ld(bufA, ln), a1 = ld(bufA, ln + 60), a2 = ld(bufA, ln + 120), a3 = ld(bufA, ln + 180);
+          wave_sync();  // in place: every lane's loads are issued before any store
+          const cplx t0 = {a0.r + a2.r, a0.i + a2.i}, t1 = {a0.r - a2.r, a0.i - a2.i};
+          const cplx t2 = {a1.r + a3.r, a1.i + a3.i}, t3 = {a1.r - a3.r, a1.i - a3.i};
+          const cplx b0 = {t0.r + t2.r, t0.i + t2.i}, b2 = {t0.r - t2.r, t0.i - t2.i};
+          const cplx b1 = {t1.r + t3.i, t1.i - t3.r}, b3 = {t1.r - t3.i, t1.i + t3.r};
+          const int o = (ln & 3) + 16 * (ln >> 2);
+          st(bufB, o, b0);
+          st(bufB, o + 4, cmul_tw(b1, w2a));
+          st(bufB, o + 8, cmul_tw(b2, w2b));
+          st(bufB, o + 12, cmul_tw(b3, w2c));
+        }
+      }
+      // stage 3 (radix 3, s = 16), 80 butterflies = two passes: both passes' loads first, then the stores (in place)
+      {
+        double2 w3[2][2];   // (stage 3's)
+#pragma unroll
+        for (int u = 0; u < 2; u++) { w3[u][0] = lc(SPX_LC_W3 + 2 * u); w3[u][1] = lc(SPX_LC_W3 + 2 * u + 1); }
+        wave_sync();
+        cplx q0[2], q1[2], q2[2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+          const int b3i = (ln + 64 * u < 80) ? ln + 64 * u : 0;
+          q0[u] = ld(bufB, b3i); q1[u] = ld(bufB, b3i + 80); q2[u] = ld(bufB, b3i + 160);
+        }
+        wave_sync();  // compiler: no store of this stage above the loads
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+          const int b3i = ln + 64 * u;
+          if (b3i < 80) {
+            const cplx a0 = q0[u], a1 = q1[u], a2 = q2[u];
+            const cplx t1 = {a1.r + a2.r, a1.i + a2.i};
+            const cplx t2 = {spx_bf3h(a0.r, t1.r), spx_bf3h(a0.i, t1.i)};
+            const cplx t3 = {S3_1 * (a1.r - a2.r), S3_1 * (a1.i - a2.i)};
+            const cplx b0 = {a0.r + t1.r, a0.i + t1.i};
+            const cplx b1 = {t2.r + t3.i, t2.i - t3.r}, b2 = {t2.r - t3.i, t2.i + t3.r};
+            const int o = (b3i & 15) + 48 * (b3i >> 4);
+            st(bufA, o, b0);
+            st(bufA, o + 16, cmul_tw(b1, w3[u][0]));
+            st(bufA, o + 32, cmul_tw(b2, w3[u][1]));
+          }
+        }
+      }
+      wave_sync();
+      // stage 4 (radix 5, s = 48, last: every twiddle is 1), in place
+      if (on48) {
+        const cplx a0 = ld(bufA, ln), a1 = ld(bufA, ln + 48), a2 = ld(bufA, ln + 96), a3 = ld(bufA, ln + 144),
+                   a4 = ld(bufA, ln + 192);
+        wave_sync();
+        const cplx t1 = {a1.r + a4.r, a1.i + a4.i}, t2 = {a2.r + a3.r, a2.i + a3.i};
+        const cplx t3 = {a1.r - a4.r, a1.i - a4.i}, t4 = {a2.r - a3.r, a2.i - a3.i};
+        const cplx b0 = {(a0.r + t1.r) + t2.r, (a0.i + t1.i) + t2.i};
+        const cplx m1 = {spx_bf5m(a0.r, C5_1, t1.r, C5_2, t2.r), spx_bf5m(a0.i, C5_1, t1.i, C5_2, t2.i)};
+        const cplx m2 = {spx_bf5m(a0.r, C5_2, t1.r, C5_1, t2.r), spx_bf5m(a0.i, C5_2, t1.i, C5_1, t2.i)};
+        const cplx n1 = {spx_bf5n(S5_1, t3.r, S5_2, t4.r), spx_bf5n(S5_1, t3.i, S5_2, t4.i)};
+        const cplx n2 = {spx_bf5d(S5_2, t3.r, S5_1, t4.r), spx_bf5d(S5_2, t3.i, S5_1, t4.i)};
+        const cplx b1 = {m1.r + n1.i, m1.i - n1.r}, b4 = {m1.r - n1.i, m1.i + n1.r};
+        const cplx b2 = {m2.r + n2.i, m2.i - n2.r}, b3 = {m2.r - n2.i, m2.i + n2.r};
+        st(bufB, ln, b0);
+        st(bufB, ln + 48, b1);
+        st(bufB, ln + 96, b2);
+        st(bufB, ln + 144, b3);
+        st(bufB, ln + 192, b4);
+      }
+      // the next slot's samples (direct) and the untangle factors: on their way while the stores drain
+      if (direct) fetch6(s + 4, nx);
+      double2 wu[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) wu[u] = lc(SPX_LC_WU + u);
+      wave_sync();
+      ASTAMP(1);
+      // untangle the packed transform:  X[k] = E[k] + e^{-2 pi i k/N} O[k]
+      float* spec_out = taps.spectrogram ? taps.spectrogram + (size_t)(S.frame_off + j) * 480 : nullptr;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int k = ln + 64 * u;
+        if (k < 240) {
+          const int k2 = (k == 0) ? 0 : 240 - k;
+          const cplx a = ld(bufB, k), c = ld(bufB, k2);
+          const double b_r = c.r, b_i = -c.i;
+          const float mag = spx_untangle_mag(a.r, a.i, b_r, b_i, wu[u]);
+          hold[u] = mag;
+          if (!keep) mrow[k] = mag;
+          if (spec_out) {
+            spec_out[k] = mag;
+            if (k > 0) spec_out[480 - k] = mag;
+            else spec_out[240] = (float)__builtin_fabs(a.r - a.i);
+          }
+        }
+      }
+      wave_sync();
+      ASTAMP(2);
+    }
+    // every wave is through its transforms: the rows over wave 0's buffer (the last slot of wave w is 12 + w, of wave 0 slot 16)
+    __syncthreads();
+    {
+      float* mrow = mags + (size_t)(wave == 0 ? TF : TF - 4 + wave) * MS;
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int k = lane + 64 * u;
+        if (k < 240) mrow[k] = hold[u];
+      }
+    }
+  } else if constexpr (WCT == 240) {
     // W = 240 = 4*4*3*5, compiled in: every butterfly index, twiddle index and loop bound is a constant of the lane, the
     // twiddles, window values and untangle factors a lane needs are loaded ONCE (they are the same for every frame) and
     // live in registers; the window / pre-emphasis pass is fused into the first radix-4 stage, whose upper two inputs
@@ -1226,7 +1441,7 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
     // ... and bring the table of log spec v2 into the work area behind the terms (the transform buffers are free by now; the
     // barrier at the end of this phase publishes it): 128 entries of 16 bytes, one per lane of waves 1 and 2
     if (tid < SPX_WAVE + 128)
-      reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(work) + terms_bytes(W, TF, WCT != 0))[tid - SPX_WAVE] =
+      reinterpret_cast<uint4*>(terms_base + terms_bytes(W, TF, WCT != 0))[tid - SPX_WAVE] =
           reinterpret_cast<const uint4*>(spx_log_table_dev)[tid - SPX_WAVE];
 #endif
   } else if (tid <= TF) {
@@ -1273,7 +1488,7 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
 
   const int nfr = j1 - j0;
 #ifndef SPX_LOG_V1
-  const SpxLogEntry* ltab = reinterpret_cast<const SpxLogEntry*>(reinterpret_cast<const unsigned char*>(work) + terms_bytes(W, TF, WCT != 0));
+  const SpxLogEntry* ltab = reinterpret_cast<const SpxLogEntry*>(terms_base + terms_bytes(W, TF, WCT != 0));
   // log spec v2 for a float quotient; anything but a positive normal float (only explicit float frames of the unit-level API can
   // produce one) takes v1, as in the oracle
   auto log_of_ratio = [&](float ratio) -> double {
@@ -1332,7 +1547,7 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
     constexpr int CB = spx_cb(TF);
     constexpr int CBS = CB + 1;
     static_assert(TF * CB == 2 * (SPX_BLOCK - SPX_WAVE), "two terms per lane of waves 1..3 and block");
-    double* tblk = work;  // [2][TF][CBS]
+    double* tblk = reinterpret_cast<double*>(terms_base);  // [2][TF][CBS]
     constexpr int NBLK = (WCT - 1 + CB - 1) / CB;
     float lsd = 0.0f;
     // What a term lane needs of its two frames is the same for every block: the two rows of magnitudes, the frame's threshold and
@@ -1574,10 +1789,13 @@ int spx_analysis_vgprs(const SpxPlanDev& P, int* scratch_bytes) {
 
 void spx_launch_analysis(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, int n_tiles,
                          const int16_t* in, SpxFrameRec* rec, SpxTapsDev taps, const int* tile_order, int* tile_flags,
-                         hipStream_t st) {
+                         bool mono, hipStream_t st) {
   if (n_tiles <= 0) return;
-  SpxLaunch<SpxAnalysisArgs>::go(spx_analysis_select(P.tile_frames, plan_ct_window(P)), n_tiles, spx_analysis_lds_bytes(P), st, P, streams,
-                                 n_streams, in, rec, taps, tile_order, tile_flags, nullptr, 0);
+  const int ctw = plan_ct_window(P);
+  // frame_mode 3: every stream is mono and the instantiation reads its samples from global memory (no staged span in its LDS)
+  const bool direct = mono && an_lean_layout(P.tile_frames, ctw);
+  SpxLaunch<SpxAnalysisArgs>::go(spx_analysis_select(P.tile_frames, ctw), n_tiles, analysis_lds_bytes(P, ctw, direct), st, P, streams,
+                                 n_streams, in, rec, taps, tile_order, tile_flags, nullptr, direct ? 3 : 0);
 }
 
 void spx_launch_analysis_frames(const SpxPlanDev& P, const SpxStreamDev* streams, int n_tiles, const float* frames,
@@ -1586,6 +1804,6 @@ void spx_launch_analysis_frames(const SpxPlanDev& P, const SpxStreamDev* streams
   SpxPlanDev Q = P;
   if (Q.tile_frames != SPX_TF_SMALL && Q.tile_frames != SPX_TF_TINY) Q.tile_frames = SPX_TF;   // (smaller tiles above about 49 / 61 kHz)
   // the plan-driven instantiation
-  SpxLaunch<SpxAnalysisArgs>::go(spx_analysis_select(Q.tile_frames, 0), n_tiles, analysis_lds_bytes(Q, false), st, Q, streams, 1, nullptr, rec,
+  SpxLaunch<SpxAnalysisArgs>::go(spx_analysis_select(Q.tile_frames, 0), n_tiles, analysis_lds_bytes(Q, 0, false), st, Q, streams, 1, nullptr, rec,
                                  taps, nullptr, nullptr, frames, preemph ? 1 : 2);
 }

@@ -63,7 +63,7 @@ int spx_debug_walk_info(int sample_rate, int channels, int n_streams, int speedu
   out[4] = c.waves;
   return 0;
 }
-// ... and the same for the analysis kernel of a rate (out[0] VGPRs, out[1] scratch bytes, out[2] LDS bytes, out[3] the plan's
+// ... and the same for the analysis kernel of a rate (out[0] VGPRs, out[1] scratch bytes, out[2] LDS bytes of a launch of mono streams, out[3] the plan's
 // transforming waves, SpxPlanDev::dft_waves) and the tension kernel
 int spx_debug_analysis_info(int sample_rate, int* out) {
   const SpxPlanDev* P = spx_internal_shared_plan(sample_rate, 0);
@@ -71,7 +71,7 @@ int spx_debug_analysis_info(int sample_rate, int* out) {
   int scratch = -1;
   out[0] = spx_analysis_vgprs(*P, &scratch);
   out[1] = scratch;
-  out[2] = (int)spx_analysis_lds_bytes(*P);
+  out[2] = (int)spx_analysis_lds_bytes(*P, /*mono=*/true);
   out[3] = P->dft_waves;
   return 0;
 }

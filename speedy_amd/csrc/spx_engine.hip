@@ -234,10 +234,18 @@ int dev_side_streams(int dev, hipStream_t* side, hipStream_t* side2) {
 }
 
 // The walk kernels of consecutive pipelined calls take turns on streams of the library's (run_impl): the device's SECOND side
-// stream -- idle in that order: the tension kernel runs behind the analysis on the first -- and one more: two walk launches in flight
-// (four streams per device in all, the caller's included: one per hardware queue of HIP's default four; more walk streams did not
-// shorten the step, profiles/r06).  Mixed calls take up to SPX_MAX_WALK_STREAMS (spx_mixed.hip).
-int walk_stream_count() { return 2; }
+// stream -- idle in that order: the tension kernel runs behind the analysis on the first -- and two more: three walk launches in
+// flight.  A walk launch lasts as long as its longest chain (1 497 steps against a mean of 1 056), and its period is launch time /
+// launches in flight; with two streams that was 1.78 / 2 = 0.89 ms, as long as the producers' chain, and a third did not pay
+// (profiles/r06).  Since the 16 kHz analysis kernel runs three workgroups to a CU (0.76 -> 0.63 ms beside the walk kernels) the
+// producers are the shorter side and the third stream shortens the step: 0.92 -> 0.84 ms (profiles/analysis_three_per_cu.txt).
+// That makes five streams per device (the caller's, the side stream, three walk streams) on HIP's default four hardware queues:
+// two of them share a queue.  Every consumer is enqueued behind its producers, so any mapping is safe; the step above was
+// measured with four queues.  Mixed calls take up to SPX_MAX_WALK_STREAMS (spx_mixed.hip).
+#ifndef SPX_WALK_STREAMS
+#define SPX_WALK_STREAMS 3   // (A/B: -DSPX_WALK_STREAMS=2; up to SPX_MAX_WALK_STREAMS)
+#endif
+int walk_stream_count() { return SPX_WALK_STREAMS; }
 int dev_walk_streams(int dev, hipStream_t* w, int n) {
   static std::mutex mu;
   static hipStream_t s3[64][SPX_MAX_WALK_STREAMS];   // [.][0] unused: the first walk stream is the second side stream
@@ -361,9 +369,9 @@ static const SpxModeResources& mode_resources(spx_plan* plan, int n, int maxC, b
   R.tile_small = spx_analysis_small_tile_frames();
   SpxPlanDev d8 = d;
   d8.tile_frames = R.tile_small;
-  R.an_lds_default = spx_analysis_lds_bytes(d);
+  R.an_lds_default = spx_analysis_lds_bytes(d, maxC == 1);
   R.an_vgprs_default = spx_analysis_vgprs(d);
-  R.an_lds_small = spx_analysis_lds_bytes(d8);
+  R.an_lds_small = spx_analysis_lds_bytes(d8, maxC == 1);
   R.an_vgprs_small = spx_analysis_vgprs(d8);
   if (plan->res_cache.size() > 64) plan->res_cache.clear();
   return plan->res_cache.emplace(key, R).first->second;
@@ -438,7 +446,7 @@ struct SpxTimed {
 //   concurrent   -- analysis and tension kernels on the device's two side streams, the walk kernel at once on the caller's:
 //                   tiles of frames, then speeds, are handed over through flags the consumers poll;
 //   ahead        -- staging, analysis and tension kernels on the side stream AT ONCE, beside the previous call's walk kernel;
-//                   the walk kernel behind them on the caller's stream, or (walk2) on one of the library's two walk streams.
+//                   the walk kernel behind them on the caller's stream, or (walk2) on one of the library's walk streams.
 int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
              int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs, bool do_a,
              bool do_w, const SpxCallOpts& opt) {
@@ -539,7 +547,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
             d.rate, n, maxC, (int)M.co_resident, (int)M.doubtful, (int)M.launch_lean, (int)M.want_concurrent, nch, tiles[0],
             concurrent ? "concurrent" : (ahead ? (M.seq_ahead ? "ahead (kernels in sequence)" : "ahead") : (chunk_ahead ? "sequence, producers ahead" : "sequence")),
             M.walk2 ? ", walk kernels overlapping" : "");
-  // the stream the walk kernel goes to: the caller's, or (walk2) one of the library's two, taking turns -- ordered behind whatever
+  // the stream the walk kernel goes to: the caller's, or (walk2) one of the library's (walk_stream_count()), taking turns -- ordered behind whatever
   // the caller had queued by the PREVIOUS call (the consumer of the output this call overwrites, two buffers taking turns) and not
   // behind this call's state of the stream, which ends with the wait for the previous call's walk kernel; a caller that hands over
   // the previous call's out / n_out again gets exactly that wait
@@ -638,7 +646,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
       hipLaunchKernelGGL(spx_gate_kernel, dim3(1), dim3(64), 0, sa, d_ready + n, n, 1200u);
     if (do_a && tiles[c] > 0) {
       SpxTimed tm(timed, 0, sa);
-      spx_launch_analysis(d, dj, n, tiles[c], in, rec, td, concurrent ? d_order : nullptr, concurrent ? d_flags : nullptr, sa);
+      spx_launch_analysis(d, dj, n, tiles[c], in, rec, td, concurrent ? d_order : nullptr, concurrent ? d_flags : nullptr, maxC == 1, sa);
     }
     if (force && force->after_analysis && c == nch - 1) HIPCHK(hipEventRecord(force->after_analysis, sa));
     if (sa != st) HIPCHK(hipEventRecord(plan->ev_chunk[c], sa));

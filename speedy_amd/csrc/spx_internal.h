@@ -50,7 +50,30 @@ struct SpxPlanDev {
   const int* perm;     // [M]  perm[p]  = g^p  mod W, g the smallest primitive root
   const int* iperm;    // [M]  iperm[q] = g^-q mod W
   const int* qlog;     // [W]  qlog[k] = the q with g^-q = k (k = 1 .. M; entry 0 unused)
+  // W = 240 only (else null): what a lane of spx_analysis_kernel<16, 240> takes from tw, tw2 and window, lane-major --
+  // entry [c][lane] at 16 bytes each, c as in spx_lane_consts_fill (spx_plan.hip) -- so that the kernel loads a group of constants
+  // right where a stage uses it (one address register, immediate offsets) instead of holding all sixty registers across the tile
+  const void* lane_consts;
 };
+// The samples' 2^-15 lives in the window values a lane multiplies by (spx_analysis.hip spx_preemph_win; -DSPX_PREEMPH_V1: the
+// literal sequence, scale 1).  A power of two: the float multiplication is exact, on the host as on the device.
+#ifdef SPX_PREEMPH_V1
+#define SPX_WIN_SCALE 1.0f
+#else
+#define SPX_WIN_SCALE 0x1p-15f
+#endif
+// The lane-major table of W = 240: 14 double2 entries (the twiddles of stages 1 - 3, the untangle factors) and one float4 (the
+// four window values times SPX_WIN_SCALE) per lane.
+#define SPX_LC_W1 0     // [3]  tw[bb j], j = 1..3, bb = lane < 60 ? lane : 0
+#define SPX_LC_W2 3     // [3]  tw[4 (bb >> 2) j]
+#define SPX_LC_W3 6     // [2][2]  tw[16 p3], tw[32 p3], p3 = (lane + 64 u) >> 4 below 80, else 0
+#define SPX_LC_WU 10    // [4]  tw2[k], k = lane + 64 u below 240, else 0
+#define SPX_LC_WN 14    // window[2 bb], [2 bb + 1], [2 bb + 120], [2 bb + 121], each times SPX_WIN_SCALE
+#define SPX_LC_ENTRIES 15
+#define SPX_LC_BYTES (SPX_LC_ENTRIES * 64 * 16)
+// fills out[SPX_LC_BYTES] from the plan's host tables (tw, tw2: (cos, -sin) pairs; win: floats) -- copies only, and the one exact
+// multiplication of the window values
+void spx_lane_consts_fill(const double* tw, const double* tw2, const float* win, unsigned char* out);
 
 // Per-stream job in device memory.  A job covers "everything new since the last call": batch jobs start
 // from scratch (SPX_F_INIT) and end the stream (SPX_F_FLUSH) in one go; the streaming API issues a job
@@ -170,9 +193,10 @@ struct SpxTapsDev {
   float* normalized;
 };
 
+// mono: as for spx_analysis_lds_bytes -- true only if NO stream of the launch has more than one channel
 void spx_launch_analysis(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, int n_tiles,
                          const int16_t* in, SpxFrameRec* rec, SpxTapsDev taps, const int* tile_order, int* tile_flags,
-                         hipStream_t st);
+                         bool mono, hipStream_t st);
 // The same kernel fed with explicit float frames (unit-level API): frame j = frames[j*W .. j*W + W), pre-emphasis state
 // carried from the previous frame's last sample (speedy.c:416-425); preemph = false: the frame is windowed as it is
 // (speedySpectrogram, speedy.c:438-473).
@@ -232,7 +256,9 @@ struct SpxWalkAsk {
 void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStreamDev* streams, const int16_t* in, int16_t* out,
                      int64_t* n_out, SpxStreamState* states, const float* scratch, const int* speed_ready, size_t lds_min,
                      hipStream_t st);
-size_t spx_analysis_lds_bytes(const SpxPlanDev& P);
+// mono: every stream of the launch has one channel (the 16 kHz 16-frame instantiation then reads its samples from global memory and
+// asks for no staged span)
+size_t spx_analysis_lds_bytes(const SpxPlanDev& P, bool mono);
 int spx_analysis_ct_window(const SpxPlanDev& P);
 // The DFT of the spec run on the host (same operation order as the kernel): used to build the Rader tables.
 void spx_host_dft(int n, const int* radix, int nstages, const double* tw, const double* in, double* out);

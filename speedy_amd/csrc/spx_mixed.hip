@@ -105,7 +105,7 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     mg.n = (int)gj[g].size();
     mg.walk = mode_walk(d, {.n_streams = mg.n, .max_channels = maxC, .speedup_only = SC.speedup_only, .any_speed = SC.any_speed});
     mg.any_nonlinear = any_nl;
-    mg.an_lds = spx_analysis_lds_bytes(d);
+    mg.an_lds = spx_analysis_lds_bytes(d, maxC == 1);
     mg.an_vgprs = spx_analysis_vgprs(d);
     G.push_back(mg);
   }

@@ -71,7 +71,7 @@ struct SpxMode {
   bool want_concurrent;
   bool concurrent;          // three kernels side by side, flags between them
   bool ahead, seq_ahead, ahead_forced;   // pipelined with the previous call (seq_ahead: its kernels otherwise in sequence)
-  bool walk2;               // ... and its walk kernel on one of the library's two walk streams
+  bool walk2;               // ... and its walk kernel on one of the library's walk streams (walk_stream_count(): three)
   bool chunk_ahead;         // a call of more than two streams per CU (time chunks, throughput-form walk kernels) whose PRODUCERS go to the
                             // side stream at once: the next call's first analysis chunk beside this call's last walk chunk (round 6)
   int nch;                  // time chunks
@@ -84,6 +84,12 @@ static inline bool spx_mode_fits2(const SpxModeResources& R, const SpxModeWalk& 
   // a stream's walk and tension workgroups and still TWO analysis workgroups on a CU, two analysis waves on a SIMD (default tile)
   return w.lds + R.tension_lds + 2 * R.an_lds_default <= lds_usable &&
          ((w.waves + 3) / 4) * w.vgprs + R.tension_vgprs + 2 * R.an_vgprs_default <= 512;
+}
+
+// analysis waves a SIMD's registers hold beside a stream's walk and tension waves (default tile)
+static inline int spx_mode_an_waves(const SpxModeResources& R, const SpxModeWalk& w) {
+  const int left = 512 - ((w.waves + 3) / 4) * w.vgprs - R.tension_vgprs;
+  return (left > 0 && R.an_vgprs_default > 0) ? left / R.an_vgprs_default : 0;
 }
 
 // One pass of the decision with the walk form given (lean or not).
@@ -188,10 +194,15 @@ static inline SpxMode spx_mode_pass(const SpxModeShape& S, const SpxModeResource
 
 // The decision.  The LEAN walk form (no output waves: one walk wave per SIMD instead of two) is taken
 //   - by necessity: where the usual form leaves no room for two analysis workgroups / waves beside it and the lean one does
-//     (22.05 kHz mono in the concurrent mode), and
+//     (22.05 kHz mono in the concurrent mode).  One case is held where it was: 16 kHz batches with slow-down jobs (walk waves
+//     of 128 registers) took the lean form because two analysis waves of 128 did not fit beside two of them; since the 16-frame
+//     16 kHz analysis kernel takes 88 registers they would, and the full form has not been measured there.  The case is told by
+//     what the kernel was built for -- its default-tile instantiation takes FEWER registers than its small-tile one, which
+//     holds for no other plan -- together with the lean form leaving room for more analysis waves than the full one (three
+//     against two; 16 kHz speed-up batches: three either way, so nothing changes for them) --, and
 //   - by preference: when the call's walk kernel WILL overlap the previous call's (walk2) with three or more workspaces taking
 //     turns -- the walk kernels have time to spare there, what the period waits for is the analysis kernel, and beside two lean
-//     walk workgroups a SIMD holds two analysis waves.  Decided AFTER `ahead` is known (round 4 decided it before, and a call
+//     walk workgroups a SIMD holds two analysis waves (three of the 16 kHz 16-frame kernel's).  Decided AFTER `ahead` is known (round 4 decided it before, and a call
 //     that then fell out of the pipelined mode ran the lean form where the full one fits).
 static inline SpxMode spx_choose_mode(const SpxModeShape& S, const SpxModeResources& R, const SpxModeEnv& E, const SpxModeRuntime& T,
                                       const SpxModeTrial& trial_in) {
@@ -199,7 +210,9 @@ static inline SpxMode spx_choose_mode(const SpxModeShape& S, const SpxModeResour
   const bool lean_possible = S.do_a && S.do_w && S.max_channels == 1 && S.n <= R.cu_count && R.walk.fast_kernel && R.walk.nwc > 0 &&
                              !S.forced && R.lean_valid && R.walk_lean.fast_kernel && R.walk_lean.nwc == 0;
   const bool lean_fits = lean_possible && spx_mode_fits2(R, R.walk_lean, lds_usable);
-  const bool need_lean = lean_fits && !spx_mode_fits2(R, R.walk, lds_usable);
+  const bool lean_analysis_build = R.tile_default == R.tile_big && R.an_vgprs_default < R.an_vgprs_small;
+  const bool need_lean = lean_fits && (!spx_mode_fits2(R, R.walk, lds_usable) ||
+                                       (lean_analysis_build && spx_mode_an_waves(R, R.walk_lean) > spx_mode_an_waves(R, R.walk)));
   SpxMode M = spx_mode_pass(S, R, E, T, trial_in, need_lean);
   if (!need_lean && lean_fits && M.walk2 && S.overlap_req && !T.two_workspaces) {
     SpxMode L = spx_mode_pass(S, R, E, T, trial_in, true);

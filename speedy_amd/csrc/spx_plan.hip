@@ -19,6 +19,48 @@ int64_t spx_internal_out_bound(const SpxPlanDev& P, int64_t n_in, float speed, b
   return (int64_t)((double)(n_in + 2 * (int64_t)P.maxRequired) * (2.0 / s)) + slack;
 }
 
+// The lane-major constants of spx_analysis_kernel<16, 240> (spx_internal.h SPX_LC_*): entry [c][lane] is the value the kernel's lane
+// would index out of tw / tw2 / win itself.
+void spx_lane_consts_fill(const double* tw, const double* tw2, const float* win, unsigned char* out) {
+  double* d = reinterpret_cast<double*>(out);   // entry (c, lane): doubles 2 (64 c + lane), 2 (64 c + lane) + 1
+  auto put = [&](int c, int lane, const double* src, int idx) {
+    d[2 * (64 * c + lane)] = src[2 * idx];
+    d[2 * (64 * c + lane) + 1] = src[2 * idx + 1];
+  };
+  for (int lane = 0; lane < 64; lane++) {
+    const int bb = lane < 60 ? lane : 0;
+    for (int j = 1; j < 4; j++) {
+      put(SPX_LC_W1 + j - 1, lane, tw, bb * j);
+      put(SPX_LC_W2 + j - 1, lane, tw, 4 * (bb >> 2) * j);
+    }
+    for (int u = 0; u < 2; u++) {
+      const int b3 = lane + 64 * u, p3 = (b3 < 80) ? (b3 >> 4) : 0;
+      put(SPX_LC_W3 + 2 * u, lane, tw, 16 * p3);
+      put(SPX_LC_W3 + 2 * u + 1, lane, tw, 32 * p3);
+    }
+    for (int u = 0; u < 4; u++) {
+      const int k = lane + 64 * u;
+      put(SPX_LC_WU + u, lane, tw2, k < 240 ? k : 0);
+    }
+    float* f = reinterpret_cast<float*>(out + 16 * (size_t)(64 * SPX_LC_WN + lane));
+    const int wi[4] = {2 * bb, 2 * bb + 1, 2 * bb + 120, 2 * bb + 121};
+    for (int k = 0; k < 4; k++) f[k] = win[wi[k]] * SPX_WIN_SCALE;
+  }
+}
+// the host tables every plan starts from: tw, tw2 [2 W doubles each], win [W floats]
+static void plan_host_tables(int W, double* tw, double* tw2, float* win) {
+  // A twiddle factor (cos, -sin)(2 pi t / den) comes from spx_twiddle.h: IEEE double operations on the integers (t, den), no libm call --
+  // the same bits on every machine (round 6; rounds 1-5 took the box's libm, round 5 "one sincos call", so GPU == oracle held on any
+  // one box only).  The Hamming window's cosine likewise (speedy.c:256-258: a double expression stored as float).
+  for (int t = 0; t < W; t++) {
+    spx_tw::entry(t, W, &tw[2 * t]);
+    spx_tw::entry(t, 2L * W, &tw2[2 * t]);
+    double c = 1.0, sn = 0.0;
+    if (W > 1) spx_tw::sincos_2pi(t, W - 1, &c, &sn);
+    win[t] = 0.54 - 0.46 * c;  // speedy.c:256-258
+  }
+}
+
 void spx_internal_set_error(const char* msg) { g_spx_err = msg ? msg : ""; }   // other translation units' errors reach spx_last_error
 extern "C" {
 
@@ -37,6 +79,16 @@ unsigned long long spx_debug_twiddle_hash(long den, long count) {
   return h;
 }
 int spx_abi_version(void) { return 1; }
+// (host-only diagnostic, no GPU needed: tests/test_lane_consts.py) the lane-major constant table of a rate whose window is 240
+// samples, as spx_plan_create builds it, and the three tables it is filled from.  out: SPX_LC_BYTES; tw, tw2: 480 doubles each;
+// win: 240 floats.  Returns the table's size in bytes, 0 if the rate has no such table, -1 on a null pointer.
+int spx_debug_lane_consts(int sample_rate, void* out, double* tw, double* tw2, float* win) {
+  if (!out || !tw || !tw2 || !win) return -1;
+  if ((int)(1.5 * sample_rate / (float)100.0) != 240) return 0;
+  plan_host_tables(240, tw, tw2, win);
+  spx_lane_consts_fill(tw, tw2, win, static_cast<unsigned char*>(out));
+  return SPX_LC_BYTES;
+}
 
 static int factor_radices(int n, int* radix) {  // DESIGN.md "DFT spec": 4s, then 2, 3s, 5s, other primes ascending
   int ns = 0;
@@ -109,7 +161,7 @@ spx_plan_t spx_plan_create(int sample_rate, int match_matlab) {
   for (int c = 0; c < 5; c++) {
     d.tile_frames = cand[c][0];
     d.dft_waves = cand[c][1];
-    if (spx_analysis_lds_bytes(d) <= 160 * 1024) break;
+    if (spx_analysis_lds_bytes(d, /*mono=*/false) <= 160 * 1024) break;
   }
   if (spx_analysis_prefers_small_tile(d)) {  // 44.1 / 48 kHz: the compiled-in kernels, two 8-frame workgroups per CU
     d.tile_frames = spx_analysis_small_tile_frames();
@@ -119,8 +171,12 @@ spx_plan_t spx_plan_create(int sample_rate, int match_matlab) {
   const size_t n_rd = rader ? 2 * (size_t)M : 0;  // doubles in each of twM and bfft
   const size_t n_ri = rader ? (size_t)M : 0;      // ints in each of perm and iperm
   const size_t n_ql = rader ? (size_t)W : 0;      // ints in qlog
-  const size_t bytes = sizeof(double) * (2 * n_tw + 2 * n_rd) + sizeof(float) * (n_win + n_tf + n_tp + 8) +
-                       sizeof(int) * (2 * n_ri + n_ql);
+  const size_t bytes0 = sizeof(double) * (2 * n_tw + 2 * n_rd) + sizeof(float) * (n_win + n_tf + n_tp + 8) +
+                        sizeof(int) * (2 * n_ri + n_ql);
+  // W = 240 (16 kHz): the lane-major constants of its 16-frame kernel behind everything else, on a 16-byte boundary
+  const bool lane_tab = !rader && W == 240;
+  const size_t off_lc = (bytes0 + 15) & ~(size_t)15;
+  const size_t bytes = lane_tab ? off_lc + SPX_LC_BYTES : bytes0;
   std::vector<unsigned char> host(bytes, 0);
   double* tw = reinterpret_cast<double*>(host.data());
   double* tw2 = tw + n_tw;
@@ -132,16 +188,8 @@ spx_plan_t spx_plan_create(int sample_rate, int match_matlab) {
   int* perm = reinterpret_cast<int*>(tp + n_tp + 8);
   int* iperm = perm + n_ri;
   int* qlog = iperm + n_ri;
-  // A twiddle factor (cos, -sin)(2 pi t / den) comes from spx_twiddle.h: IEEE double operations on the integers (t, den), no libm call --
-  // the same bits on every machine (round 6; rounds 1-5 took the box's libm, round 5 "one sincos call", so GPU == oracle held on any
-  // one box only).  The Hamming window's cosine likewise (speedy.c:256-258: a double expression stored as float).
-  for (int t = 0; t < W; t++) {
-    spx_tw::entry(t, W, &tw[2 * t]);
-    spx_tw::entry(t, 2L * W, &tw2[2 * t]);
-    double c = 1.0, sn = 0.0;
-    if (W > 1) spx_tw::sincos_2pi(t, W - 1, &c, &sn);
-    win[t] = 0.54 - 0.46 * c;  // speedy.c:256-258
-  }
+  plan_host_tables(W, tw, tw2, win);
+  if (lane_tab) spx_lane_consts_fill(tw, tw2, win, host.data() + off_lc);
   if (rader) {
     for (int t = 0; t < M; t++) spx_tw::entry(t, M, &twM[2 * t]);
     int g = 2;  // smallest primitive root of W
@@ -200,6 +248,7 @@ spx_plan_t spx_plan_create(int sample_rate, int match_matlab) {
   d.perm = reinterpret_cast<const int*>(d.taperP + n_tp + 8);
   d.iperm = d.perm + n_ri;
   d.qlog = d.iperm + n_ri;
+  d.lane_consts = lane_tab ? base + off_lc : nullptr;   // (hipMalloc's base is aligned far beyond 16 bytes)
   return p;
 }
 
@@ -245,7 +294,7 @@ int64_t spx_plan_out_capacity(spx_plan_t p, int64_t n_in, float speed) {
 }
 
 }  // extern "C"
-bool spx_internal_analysis_fits(const SpxPlanDev& d) { return spx_analysis_lds_bytes(d) <= 160 * 1024; }
+bool spx_internal_analysis_fits(const SpxPlanDev& d) { return spx_analysis_lds_bytes(d, /*mono=*/false) <= 160 * 1024; }
 
 spx_plan* shared_plan_full(int sample_rate, int match_matlab) {
   static std::mutex mu;
