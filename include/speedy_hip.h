@@ -137,7 +137,8 @@ int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, f
  * int16 call's own workspace, so spx_batch_read_steps works on it; behind it lie the table and the two stagings.
  * Refused with -1 and spx_last_error, nothing launched: everything the int16 call refuses (a bad speed, rate, nonlinear factor ...),
  * a null pointer, in or out not 4-byte aligned, a workspace that is too small.
- * NOT offered on float samples: the _ahead / _overlapped / _mixed* forms, the pipeline object, spx_batch_pack_outputs. */
+ * NOT offered on float samples: the _ahead / _overlapped / _mixed* forms on caller-owned buffers and spx_batch_pack_outputs.  (The
+ * pipeline object takes float samples: SPX_PIPELINE_FLOAT below.) */
 size_t spx_batch_workspace_bytes_float(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams);
 int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, const float* in,
                         float* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
@@ -207,11 +208,15 @@ int spx_batch_run_ahead_when(spx_plan_t plan, const spx_stream_job* jobs, int n_
  *   depth     buffer sets, 2 .. 8 (0 = the default, 4); 3 or more let the walk kernels of consecutive batches overlap fully
  *   flags     SPX_PIPELINE_DEVICE_OUT: the outputs stay in device memory (no gather, no copy out).  Such a pipeline's calls are
  *             detached from its run stream, and since round 6 that holds for mixed-rate batches too: the groups' walk kernels of
- *             consecutive batches overlap on the library's walk streams (BASELINE configs[4] shard: 1.87 - 1.97 -> 1.56 ms per batch)
+ *             consecutive batches overlap on the library's walk streams (BASELINE configs[4] shard: 1.87 - 1.97 -> 1.56 ms per batch).
+ *             With SPX_PIPELINE_FLOAT as well the output conversion runs behind a batch's walk kernel, so such a batch cannot be
+ *             detached: it takes the engine order the host-output pipeline takes.
+ *             SPX_PIPELINE_FLOAT: a pipeline on float samples (the _float calls further down); combines with the above.
  * NULL with spx_last_error ("spx_pipeline: lane N: " and the rule) for a creation table with a job spx_batch_run would refuse.
  * Not thread-safe: one host thread (or external locking) per pipeline; several pipelines may be alive at once. */
 typedef struct spx_pipeline* spx_pipeline_t;
 #define SPX_PIPELINE_DEVICE_OUT 1u
+#define SPX_PIPELINE_FLOAT 2u   /* flags of spx_pipeline_create / spx_pipeline_create_mixed; combines with SPX_PIPELINE_DEVICE_OUT */
 spx_pipeline_t spx_pipeline_create(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, int depth, unsigned flags);
 spx_pipeline_t spx_pipeline_create_mixed(const spx_plan_t* plans, int n_plans, const spx_stream_job* jobs, const int* plan_index,
                                          int n_streams, int depth, unsigned flags);
@@ -262,7 +267,9 @@ int64_t spx_pipeline_submit_jobs(spx_pipeline_t p, const spx_stream_job* jobs, c
  * waits for nothing. */
 int spx_pipeline_jobs_fit(spx_pipeline_t p, const spx_stream_job* jobs);
 /* Blocks until the input handed over with `ticket` may be overwritten: the copy in has finished (host input), the batch's kernels
- * have finished (device input: they read it to the end).  0, or a negative error (unknown ticket). */
+ * have finished (device input: they read it to the end).  On a float pipeline (SPX_PIPELINE_FLOAT) an input of EITHER kind is
+ * consumed once its conversion has run -- the call returns then, not at the end of the batch: a device tensor may be reused a whole
+ * batch earlier than on an int16 pipeline.  0, or a negative error (unknown ticket). */
 int spx_pipeline_input_consumed(spx_pipeline_t p, int64_t ticket);
 /* Wait for a batch.  On return
  *   *out      the output samples: pinned HOST memory owned by the pipeline (DEVICE memory with SPX_PIPELINE_DEVICE_OUT)
@@ -273,6 +280,40 @@ int spx_pipeline_input_consumed(spx_pipeline_t p, int64_t ticket);
  * valid until `depth` more batches have been submitted.  Tickets may be waited for in any order, each at most once per buffer
  * life; a ticket whose buffers have been handed to a later batch returns an error. */
 int spx_pipeline_wait(spx_pipeline_t p, int64_t ticket, const int16_t** out, const int64_t** offsets, const int64_t** counts);
+
+/* ---- the pipeline object on FLOAT samples: spx_pipeline_create / _create_mixed with SPX_PIPELINE_FLOAT ----
+ * sonicWriteFloatToStream / sonicReadFloatFromStream (sonic2.h:64-68) for a caller that feeds batches of float audio -- a loader's
+ * float32 in host memory, a model's waveform in device memory -- with both conversions on the GPU, inside the pipeline's own order.
+ * CREATION AND FIT are those of every pipeline: the same tables, the same capacity rules, the same "lane N:" messages;
+ * spx_pipeline_input_values() counts FLOAT values and is the same number as for int16; in_off counts float values inside `in`;
+ * spx_pipeline_jobs_fit works unchanged.  The conversions do not depend on a plan: spx_pipeline_create_mixed takes the flag too.
+ * INPUT CONVERSION: spx_batch_run_float's rule exactly, per lane, by the nonlinear factor of THIS BATCH's job: nonlinear != 0 gives
+ * (double)x * 32768.0, nonlinear == 0 gives x * 32767.0f; then truncate toward zero to 32 bits and keep the low 16 bits; a product
+ * that is NaN or of magnitude >= 2^31 gives 0.  OUTPUT: every value is an int16 / 32767.0f, the IEEE quotient.
+ * What a submit enqueues, without a host wait beyond the one for the batch `depth` tickets back: on the pipeline's copy stream the
+ * copy in (host input), this batch's conversion table and one conversion launch over (block, lane) into the int16 staging the engine
+ * reads; the engine as for an int16 batch; and on the run stream a gather kernel that converts while it packs and writes floats
+ * straight into pinned host memory (SPX_PIPELINE_DEVICE_OUT: a conversion behind the walk kernel into a float buffer on the device).
+ *   HOST input    is copied up to the batch's extent only: extent x 4 bytes (spx_pipeline_submit_float: the creation table's).
+ *   DEVICE input  is read exactly over the jobs' values, by the conversion and not by the walk kernel's window loads: NO 64-value
+ *                 padding is needed, only 4-byte alignment; complete when the call is made, unchanged until
+ *                 spx_pipeline_input_consumed (above: it returns once the conversion has run, for either kind of input).
+ * spx_pipeline_wait_float, host output: *out is pinned HOST memory holding floats; *offsets count float values and, with *counts,
+ * are the SAME NUMBERS the int16 pipeline reports for the same batch -- every offset a multiple of 32 values, here 128 bytes; an empty
+ * lane takes no room; the values between a stream's last frame and the next offset are unspecified.  With SPX_PIPELINE_DEVICE_OUT:
+ * *out is a float buffer in DEVICE memory in the static capacity layout (the creation offsets), *counts are in device memory.
+ * A negative count converts min(|count|, capacity) frames and a lost producer none, as in the int16 gather.
+ * WRONG-KIND CALLS -- spx_pipeline_submit, _submit_jobs, _wait, _host_input on a float pipeline; the _float calls on an int16 one --
+ * return -1 (NULL) with a message that names the flag, before anything is waited for, copied or enqueued: no ticket is used up and
+ * the pipeline stays fully usable.  A float pointer that is not 4-byte aligned is refused the same way.
+ * STILL OUT OF SCOPE: playback rates in the pipeline, float _ahead / _overlapped / _mixed* calls on caller-owned buffers, a float
+ * spx_batch_pack_outputs. */
+/* Pinned host staging of spx_pipeline_input_values() floats for the next submit, as spx_pipeline_host_input. */
+float* spx_pipeline_host_input_float(spx_pipeline_t p);
+int64_t spx_pipeline_submit_float(spx_pipeline_t p, const float* in, int in_is_device);
+int64_t spx_pipeline_submit_jobs_float(spx_pipeline_t p, const spx_stream_job* jobs, const float* in, int in_is_device);
+int spx_pipeline_wait_float(spx_pipeline_t p, int64_t ticket, const float** out, const int64_t** offsets, const int64_t** counts);
+
 /* Pinned host memory for callers without HIP headers (the input of spx_pipeline_submit at the full link rate). */
 void* spx_host_alloc(size_t bytes);
 void spx_host_free(void* p);

@@ -101,6 +101,10 @@ SYMBOLS = {
     "spx_pipeline_jobs_fit": (C.c_int, [C.c_void_p, C.POINTER(StreamJob)]),
     "spx_pipeline_input_consumed": (C.c_int, [C.c_void_p, C.c_int64]),
     "spx_pipeline_wait": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "spx_pipeline_host_input_float": (C.c_void_p, [C.c_void_p]),
+    "spx_pipeline_submit_float": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int]),
+    "spx_pipeline_submit_jobs_float": (C.c_int64, [C.c_void_p, C.POINTER(StreamJob), C.c_void_p, C.c_int]),
+    "spx_pipeline_wait_float": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "spx_host_alloc": (C.c_void_p, [C.c_size_t]),
     "spx_host_free": (None, [C.c_void_p]),
     "spx_device_alloc": (C.c_void_p, [C.c_size_t]),

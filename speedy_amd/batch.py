@@ -469,9 +469,20 @@ class Pipeline:
 
         t = pipe.submit_jobs(pipe.pack(xs, lens), lens, speed=speeds)
 
-    plans / plan_index: a batch that mixes sample rates (spx_pipeline_create_mixed); a lane's plan and channel count are fixed."""
+    plans / plan_index: a batch that mixes sample rates (spx_pipeline_create_mixed); a lane's plan and channel count are fixed.
 
-    def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, depth=0, device_out=False, plan_index=None):
+    float_samples: a pipeline on FLOAT samples in (-1, 1) (SPX_PIPELINE_FLOAT): pack, host_input, submit, submit_jobs, wait and
+    results work on float32 -- numpy arrays, pinned torch tensors, CUDA tensors -- with both conversions on the GPU, by FloatBatch's
+    rules (the input scale per lane by the nonlinear factor of the batch's job, every output value an int16 / 32767.0f).  A CUDA
+    tensor needs numel() >= the batch's extent only: no padding."""
+
+    def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, depth=0, device_out=False, plan_index=None,
+                 float_samples=False):
+        if float_samples and not torch.cuda.is_available():
+            raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
+        self.float_samples = bool(float_samples)
+        self._np_dt, self._torch_dt, self._c_dt = ((np.float32, torch.float32, C.c_float) if float_samples else
+                                                   (np.int16, torch.int16, C.c_int16))
         plans = list(plan) if isinstance(plan, (list, tuple)) else [plan]
         self.plans = plans
         self.L = plans[0].L
@@ -494,7 +505,7 @@ class Pipeline:
             in_off += int(self.lengths[i]) * int(ch[i])
         self.total_in = in_off
         self.device_out = bool(device_out)
-        flags = 1 if device_out else 0
+        flags = (1 if device_out else 0) | (2 if float_samples else 0)   # SPX_PIPELINE_DEVICE_OUT | SPX_PIPELINE_FLOAT
         if plan_index is None and len(plans) == 1:
             self.h = self.L.spx_pipeline_create(plans[0].h, self.jobs, n, int(depth), flags)
         else:
@@ -508,30 +519,32 @@ class Pipeline:
         self._keep = {}   # ticket -> the input object (host memory must stay alive until its copy has been made)
 
     def pack(self, streams, lengths=None):
-        """One batch's input as the pipeline expects it: the streams (int16 numpy arrays, interleaved) each at its lane's offset.
-        lengths: this batch's frames per lane (submit_jobs) -- shorter streams start where the lane starts."""
+        """One batch's input as the pipeline expects it: the streams (int16 numpy arrays, interleaved; float32 on a float pipeline)
+        each at its lane's offset.  lengths: this batch's frames per lane (submit_jobs) -- shorter streams start where the lane starts."""
         lengths = self.lengths if lengths is None else lengths
-        host = np.zeros(self.total_in, np.int16)
+        host = np.zeros(self.total_in, self._np_dt)
         for i, x in enumerate(streams):
-            x = np.ascontiguousarray(x, np.int16).ravel()
+            x = np.ascontiguousarray(x, self._np_dt).ravel()
             assert x.size == int(lengths[i]) * int(self.channels[i]) <= int(self.lengths[i]) * int(self.channels[i])
             host[self.in_offs[i]:self.in_offs[i] + x.size] = x
         return host
 
     def host_input(self):
-        """The pinned staging buffer of the NEXT submit as an int16 numpy view (fill it, then submit(it))."""
-        ptr = self.L.spx_pipeline_host_input(self.h)
+        """The pinned staging buffer of the NEXT submit as an int16 (float32) numpy view (fill it, then submit(it))."""
+        ptr = (self.L.spx_pipeline_host_input_float if self.float_samples else self.L.spx_pipeline_host_input)(self.h)
         if not ptr:
             raise RuntimeError("spx_pipeline_host_input: " + self.L.spx_last_error().decode())
-        return np.ctypeslib.as_array((C.c_int16 * self.total_in).from_address(ptr))
+        return np.ctypeslib.as_array((self._c_dt * self.total_in).from_address(ptr))
 
     def _input_ptr(self, x, extent):
         if isinstance(x, torch.Tensor):
-            assert x.dtype == torch.int16 and x.is_contiguous() and x.numel() >= extent
-            # (include/speedy_hip.h: a device input is used in place and must be allocated 64 values past the last stream's end)
-            assert not x.is_cuda or x.numel() >= self.total_in + 64, "device input: allocate spx_pipeline_input_values() + 64 int16 values"
+            assert x.dtype == self._torch_dt and x.is_contiguous() and x.numel() >= extent
+            # (include/speedy_hip.h: an int16 device input is used in place and must be allocated 64 values past the last stream's end;
+            # a float one is read by the conversion, exactly over the jobs' values)
+            assert self.float_samples or not x.is_cuda or x.numel() >= self.total_in + 64, \
+                "device input: allocate spx_pipeline_input_values() + 64 int16 values"
             return x, x.data_ptr(), x.is_cuda
-        x = np.ascontiguousarray(x, np.int16)
+        x = np.ascontiguousarray(x, self._np_dt)
         assert x.size >= extent
         return x, x.ctypes.data, False
 
@@ -545,7 +558,8 @@ class Pipeline:
     def submit(self, x, device=False):
         x, ptr, dev = self._input_ptr(x, self.total_in)
         device = dev if isinstance(x, torch.Tensor) else device
-        return self._ticket(self.L.spx_pipeline_submit(self.h, ptr, 1 if device else 0), x, "spx_pipeline_submit")
+        call = self.L.spx_pipeline_submit_float if self.float_samples else self.L.spx_pipeline_submit
+        return self._ticket(call(self.h, ptr, 1 if device else 0), x, "spx_pipeline_submit")
 
     def table(self, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None):
         """The job table of one batch (spx_stream_job[n], host): None = the value the lane was created with."""
@@ -575,29 +589,33 @@ class Pipeline:
         extent = min(self.total_in, max(int(j.in_off) + int(j.n_in) * int(j.channels) for j in jobs))
         x, ptr, dev = self._input_ptr(x, extent)
         device = dev if isinstance(x, torch.Tensor) else device
-        return self._ticket(self.L.spx_pipeline_submit_jobs(self.h, jobs, ptr, 1 if device else 0), x, "spx_pipeline_submit_jobs")
+        call = self.L.spx_pipeline_submit_jobs_float if self.float_samples else self.L.spx_pipeline_submit_jobs
+        return self._ticket(call(self.h, jobs, ptr, 1 if device else 0), x, "spx_pipeline_submit_jobs")
 
     def input_consumed(self, ticket):
-        """Blocks until the input handed over with `ticket` may be overwritten (host input: copied in; device input: batch done)."""
+        """Blocks until the input handed over with `ticket` may be overwritten (host input: copied in; device input: batch done;
+        a float pipeline's input of either kind: converted)."""
         if self.L.spx_pipeline_input_consumed(self.h, int(ticket)) != 0:
             raise RuntimeError("spx_pipeline_input_consumed: " + self.L.spx_last_error().decode())
 
     def wait(self, ticket):
         """(out, offsets, counts) of a batch: numpy views of the pipeline's pinned host buffers -- device_out: (data pointer of the
-        int16 output in device memory, offsets as a numpy array, data pointer of the int64 counts in device memory)."""
+        int16 output in device memory, offsets as a numpy array, data pointer of the int64 counts in device memory).  A float
+        pipeline: float32 in place of int16, the same offsets and counts."""
         o, f, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        rc = self.L.spx_pipeline_wait(self.h, int(ticket), C.byref(o), C.byref(f), C.byref(c))
+        call = self.L.spx_pipeline_wait_float if self.float_samples else self.L.spx_pipeline_wait
+        rc = call(self.h, int(ticket), C.byref(o), C.byref(f), C.byref(c))
         if rc != 0:
             raise RuntimeError("spx_pipeline_wait: " + self.L.spx_last_error().decode())
         offsets = np.ctypeslib.as_array((C.c_int64 * (self.n + 1)).from_address(f.value))
         if self.device_out:
             return o.value, offsets, c.value
         counts = np.ctypeslib.as_array((C.c_int64 * self.n).from_address(c.value))
-        out = np.ctypeslib.as_array((C.c_int16 * max(1, int(offsets[self.n]))).from_address(o.value))
+        out = np.ctypeslib.as_array((self._c_dt * max(1, int(offsets[self.n]))).from_address(o.value))
         return out, offsets, counts
 
     def results(self, ticket):
-        """Per-stream int16 outputs of a batch (copies; raises on overflow / a lost producer)."""
+        """Per-stream int16 (float32) outputs of a batch (copies; raises on overflow / a lost producer)."""
         out, offsets, counts = self.wait(ticket)
         if self.device_out:
             cnt = torch.empty(self.n, dtype=torch.int64)
@@ -605,8 +623,8 @@ class Pipeline:
             self.L.spx_stream_synchronize(None)
             counts = cnt.numpy()
             total = int(offsets[self.n])
-            host = torch.empty(total, dtype=torch.int16)
-            self.L.spx_copy_to_host(host.data_ptr(), out, total * 2, None)
+            host = torch.empty(total, dtype=self._torch_dt)
+            self.L.spx_copy_to_host(host.data_ptr(), out, total * host.element_size(), None)
             self.L.spx_stream_synchronize(None)
             out = host.numpy()
         if (counts < 0).any():

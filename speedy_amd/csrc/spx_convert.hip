@@ -144,6 +144,63 @@ static int64_t conv_blocks(int64_t vals) {
   return (vals + (SPX_CV_VALUES - 1) + per - 1) / per;
 }
 
+// The conversion table of a job table, written into `tab` (pinned host memory), and the two grids' first dimensions.  -1: a stream
+// has more values than one launch covers.
+static int conv_fill(SpxConvJob* tab, const spx_stream_job* jobs, int n, int* max_in, int* max_out) {
+  int64_t mi = 1, mo = 1;
+  for (int i = 0; i < n; i++) {
+    const spx_stream_job& j = jobs[i];
+    SpxConvJob& J = tab[i];
+    J.in_off = j.in_off; J.in_vals = j.n_in * j.channels;
+    J.out_off = j.out_off; J.out_cap = j.out_cap;
+    J.channels = j.channels; J.nonlinear = j.nonlinear != 0.0f ? 1 : 0;
+    const int64_t bi = conv_blocks(J.in_vals), bo = conv_blocks(j.out_cap * j.channels);
+    if (bi > 0x7fffffff || bo > 0x7fffffff) return -1;
+    J.in_blocks = J.in_vals > 0 ? (int)bi : 0;
+    J.out_blocks = j.out_cap > 0 ? (int)bo : 0;
+    mi = std::max<int64_t>(mi, J.in_blocks);
+    mo = std::max<int64_t>(mo, J.out_blocks);
+  }
+  *max_in = (int)mi; *max_out = (int)mo;
+  return 0;
+}
+static void conv_upload(const void* pinned, SpxConvJob* d_tab, int n, hipStream_t st) {
+  const unsigned words = (unsigned)(sizeof(SpxConvJob) * (size_t)n / sizeof(unsigned));
+  hipLaunchKernelGGL(spx_conv_table_kernel, dim3((words + 255) / 256 < 64 ? (words + 255) / 256 : 64), dim3(256), 0, st,
+                     static_cast<const unsigned*>(pinned), reinterpret_cast<unsigned*>(d_tab), words);
+}
+static void conv_launch_in(const SpxConvJob* d_tab, int n, int max_in, const float* in, int16_t* st_in, hipStream_t st) {
+  SpxConvJob none;
+  memset(&none, 0, sizeof(none));
+  for (int s0 = 0; s0 < n; s0 += 65535) {   // (the grid's second dimension holds 65 535)
+    const int m = n - s0 < 65535 ? n - s0 : 65535;
+    hipLaunchKernelGGL(spx_float_to_short_kernel, dim3((unsigned)max_in, (unsigned)m), dim3(SPX_CV_THREADS), 0, st, d_tab, none, s0, in, st_in);
+  }
+}
+static void conv_launch_out(const SpxConvJob* d_tab, int n, int max_out, const int64_t* n_out, const int16_t* st_out, float* out, hipStream_t st) {
+  SpxConvJob none;
+  memset(&none, 0, sizeof(none));
+  for (int s0 = 0; s0 < n; s0 += 65535) {
+    const int m = n - s0 < 65535 ? n - s0 : 65535;
+    hipLaunchKernelGGL(spx_short_to_float_kernel, dim3((unsigned)max_out, (unsigned)m), dim3(SPX_CV_THREADS), 0, st, d_tab, none, s0, n_out,
+                       st_out, out);
+  }
+}
+
+// The same four steps for the pipeline object on float samples (spx_pipeline.hip, SPX_PIPELINE_FLOAT): the table lives in a buffer
+// set's own pinned and device memory, the stagings are the buffer set's d_in / d_out.  The kernels and their arithmetic are these.
+size_t spx_conv_table_bytes(int n) { return sizeof(SpxConvJob) * (size_t)n; }
+int spx_conv_table_fill(void* pinned, const spx_stream_job* jobs, int n, int* max_in, int* max_out) {
+  return conv_fill(static_cast<SpxConvJob*>(pinned), jobs, n, max_in, max_out);
+}
+void spx_conv_table_upload(const void* pinned, void* d_tab, int n, hipStream_t st) { conv_upload(pinned, static_cast<SpxConvJob*>(d_tab), n, st); }
+void spx_conv_launch_in(const void* d_tab, int n, int max_in, const float* in, int16_t* st_in, hipStream_t st) {
+  conv_launch_in(static_cast<const SpxConvJob*>(d_tab), n, max_in, in, st_in, st);
+}
+void spx_conv_launch_out(const void* d_tab, int n, int max_out, const int64_t* n_out, const int16_t* st_out, float* out, hipStream_t st) {
+  conv_launch_out(static_cast<const SpxConvJob*>(d_tab), n, max_out, n_out, st_out, out, st);
+}
+
 // Workspace of a float call: the int16 call's own workspace at the front (spx_batch_read_steps finds its records there) |
 // SpxConvJob[n] | the int16 input staging, max(in_off + n_in * channels) + 64 values (the padding the kernels' window loads may
 // touch) | the int16 output staging, max(out_off + out_cap * channels) values; every part on a 256-byte boundary.
@@ -239,41 +296,17 @@ int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float
     HIPCHK(hipHostMalloc(&G.p, need * 2 + 1024, hipHostMallocDefault));
     G.cap = need * 2 + 1024;
   }
-  SpxConvJob* tab = static_cast<SpxConvJob*>(G.p);
-  int64_t max_in = 1, max_out = 1;
-  for (int i = 0; i < n; i++) {
-    const spx_stream_job& j = jobs[i];
-    SpxConvJob& J = tab[i];
-    J.in_off = j.in_off; J.in_vals = j.n_in * j.channels;
-    J.out_off = j.out_off; J.out_cap = j.out_cap;
-    J.channels = j.channels; J.nonlinear = j.nonlinear != 0.0f ? 1 : 0;
-    const int64_t bi = conv_blocks(J.in_vals), bo = conv_blocks(j.out_cap * j.channels);
-    if (bo > 0x7fffffff) return fail(-1, "spx_batch_run_float: out_cap too large for one launch");
-    J.in_blocks = J.in_vals > 0 ? (int)bi : 0;
-    J.out_blocks = j.out_cap > 0 ? (int)bo : 0;
-    max_in = std::max<int64_t>(max_in, J.in_blocks);
-    max_out = std::max<int64_t>(max_out, J.out_blocks);
-  }
+  int max_in = 1, max_out = 1;
+  if (conv_fill(static_cast<SpxConvJob*>(G.p), jobs, n, &max_in, &max_out)) return fail(-1, "spx_batch_run_float: out_cap too large for one launch");
   SpxRange range_("spx_batch_run_float");
-  const unsigned words = (unsigned)(need / sizeof(unsigned));
-  hipLaunchKernelGGL(spx_conv_table_kernel, dim3((words + 255) / 256 < 64 ? (words + 255) / 256 : 64), dim3(256), 0, st,
-                     reinterpret_cast<const unsigned*>(G.p), reinterpret_cast<unsigned*>(d_tab), words);
+  conv_upload(G.p, d_tab, n, st);
   HIPCHK(hipEventRecord(G.done, st));
 
   // ---- input conversion | the int16 call on the stagings | output conversion, all on hip_stream ----
-  SpxConvJob none;
-  memset(&none, 0, sizeof(none));
-  for (int s0 = 0; s0 < n; s0 += 65535) {   // (the grid's second dimension holds 65 535)
-    const int m = n - s0 < 65535 ? n - s0 : 65535;
-    hipLaunchKernelGGL(spx_float_to_short_kernel, dim3((unsigned)max_in, (unsigned)m), dim3(SPX_CV_THREADS), 0, st, d_tab, none, s0, in, st_in);
-  }
+  conv_launch_in(d_tab, n, max_in, in, st_in, st);
   const int rc = spx_batch_run_rate(plan, jobs, rates, n, st_in, st_out, n_out, ws, FL.base, taps, hs);
   if (rc) return rc;
-  for (int s0 = 0; s0 < n; s0 += 65535) {
-    const int m = n - s0 < 65535 ? n - s0 : 65535;
-    hipLaunchKernelGGL(spx_short_to_float_kernel, dim3((unsigned)max_out, (unsigned)m), dim3(SPX_CV_THREADS), 0, st, d_tab, none, s0, n_out,
-                       st_out, out);
-  }
+  conv_launch_out(d_tab, n, max_out, n_out, st_out, out, st);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -26,6 +26,23 @@
 // from the last batch that came back (the rest of a batch that outgrew the copy fetched at wait time) -- the runtime performs
 // that copy with its full-width shader kernel (__amd_rocclr_copyBuffer, 0.53 - 0.56 ms per 27 MB), and the leg read 1.78 - 1.83 ms
 // per batch against 1.67 - 1.70.  Not kept.
+//
+// FLOAT samples (SPX_PIPELINE_FLOAT): the same pipeline with a conversion at either end; the engine, its kernels and the int16
+// buffers between them are untouched, and a pipeline without the flag takes none of this code.
+//   copy stream   [H2D of extent x 4 bytes into the slot's float staging]  ->  this batch's conversion table (spx_convert.hip's
+//                 SpxConvJob records: in_off, values and scale per lane, from the slot's pinned copy)  ->  spx_float_to_short_kernel
+//                 over (block, lane) into the slot's int16 staging  ->  record(in)
+//   run stream    host output: spx_pipe_copy_float_kernel instead of spx_pipe_copy_kernel -- it converts while it packs and writes
+//                 floats straight into the slot's pinned float buffer;  SPX_PIPELINE_DEVICE_OUT: spx_short_to_float_kernel (the form
+//                 that reads n_out on the device) behind the walk kernel into the slot's float d_out
+// The input conversion goes on the COPY stream, not behind `in` on the run stream or one of the engine's: it is the natural
+// continuation of the copy it depends on (stream order, no event between them), `in` then means "the int16 staging is complete" and
+// the engine is called exactly as for an int16 batch -- and the run stream's head is the previous batch's gather, which waits for
+// that batch's walk kernel: a conversion queued there would hold this batch's producers back by a whole batch.  A device input is
+// converted there too (nothing to copy): the conversion, not the walk kernel's window loads, reads the caller's buffer, exactly over
+// the jobs' values, and `in` says when it has been read.  No stream is added to the five the library holds.
+// Measured (profiles/pipeline_float.txt, 256 x 10 s): the conversions take 55 and 24 us, the float gather 0.99 ms for 53.5 MB (the int16
+// one 0.49 for half the bytes: the link's rate both); host to host 3.36 ms per batch over a 2.88 ms copy of the 164 MB input.
 #include <string.h>
 
 #include <string>
@@ -42,6 +59,12 @@ int spx_internal_run_mixed(const spx_plan_t* plans, int n_plans, const spx_strea
                            int16_t* out, int64_t* n_out, void* ws, size_t ws_bytes, void* hs, bool ahead, void* in_ready,
                            void* done_event, bool detached);
 void spx_internal_set_error(const char* msg);
+// spx_convert.hip: the float batch call's conversion table and its two kernels, launched for a buffer set of the pipeline's
+size_t spx_conv_table_bytes(int n);
+int spx_conv_table_fill(void* pinned, const spx_stream_job* jobs, int n, int* max_in, int* max_out);
+void spx_conv_table_upload(const void* pinned, void* d_tab, int n, hipStream_t st);
+void spx_conv_launch_in(const void* d_tab, int n, int max_in, const float* in, int16_t* st_in, hipStream_t st);
+void spx_conv_launch_out(const void* d_tab, int n, int max_out, const int64_t* n_out, const int16_t* st_out, float* out, hipStream_t st);
 
 #define SPX_PIPE_MAX_DEPTH 8
 #define PIPE_ALIGN 32   // int16 values: every stream's region starts at a 64-byte boundary, in device and in host memory
@@ -102,6 +125,37 @@ spx_pipe_copy_kernel(const int16_t* __restrict__ out, const int64_t* __restrict_
     }
   }
 }
+// The same on float samples: per step a lane loads one 16-byte vector of 8 int16 and stores two 16-byte vectors of floats, every
+// value int16 / 32767.0f (the IEEE quotient: -fhip-fp32-correctly-rounded-divide-sqrt, as spx_short_to_float_kernel has it).  The
+// packed offsets count values, so a stream's floats start at a 128-byte boundary of dst; the last vectors of a stream may carry the
+// images of up to 31 capacity-region values -- dst holds out_values + 64 floats.
+typedef short spx_pipe_short8 __attribute__((ext_vector_type(8)));
+typedef float spx_pipe_float4 __attribute__((ext_vector_type(4)));
+__global__ void __launch_bounds__(256)
+spx_pipe_copy_float_kernel(const int16_t* __restrict__ out, const int64_t* __restrict__ out_offs, const int64_t* __restrict__ d_offsets, int n,
+                           float* __restrict__ dst) {
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    const spx_pipe_short8* __restrict__ s = reinterpret_cast<const spx_pipe_short8*>(out + out_offs[i]);
+    spx_pipe_float4* __restrict__ d = reinterpret_cast<spx_pipe_float4*>(dst + d_offsets[i]);
+    const int64_t nv = (d_offsets[i + 1] - d_offsets[i]) / 8;   // 16-byte vectors of the source
+    for (int64_t e0 = threadIdx.x; e0 < nv; e0 += 4 * 256) {
+      spx_pipe_short8 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) { const int64_t e = e0 + u * 256; if (e < nv) v[u] = s[e]; }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int64_t e = e0 + u * 256;
+        if (e < nv) {
+          spx_pipe_float4 a, b;
+#pragma unroll
+          for (int k = 0; k < 4; k++) { a[k] = (float)v[u][k] / 32767.0f; b[k] = (float)v[u][4 + k] / 32767.0f; }
+          d[2 * e] = a;
+          d[2 * e + 1] = b;
+        }
+      }
+    }
+  }
+}
 
 struct SpxPipeSlot {
   int16_t* d_in = nullptr;
@@ -116,9 +170,17 @@ struct SpxPipeSlot {
   hipEvent_t ev_done = nullptr;   // kernels and gather done: the output is in host memory, d_in / d_out may be reused
   std::vector<spx_stream_job> jobs;   // the table this ticket was submitted with (the pipeline's out_off / out_cap in it): kept for the
                                       // record -- the engine stages what it needs before its call returns, nothing reads this later
+  // SPX_PIPELINE_FLOAT (everything below stays null without the flag)
+  float* d_inf = nullptr;         // float staging of a host input, allocated on first use as d_in is
+  float* d_outf = nullptr;        // SPX_PIPELINE_DEVICE_OUT: the float output in the static layout
+  float* h_inf = nullptr;         // pinned float staging a caller may fill (spx_pipeline_host_input_float)
+  float* h_outf = nullptr;        // pinned: the packed float output (no h_out then)
+  void* h_cv = nullptr;           // pinned: this ticket's conversion table, and its device copy
+  void* d_cv = nullptr;
   int64_t ticket = -1;
   bool in_recorded = false;       // ev_in has been recorded at least once (h_in / d_in have a copy to wait for)
-  bool in_host = false;           // this ticket's input came from host memory: consumed once ev_in has passed (device input: ev_done)
+  bool in_host = false;           // this ticket's input came from host memory: consumed once ev_in has passed (device input: ev_done);
+                                  // set for a float input of either kind: its conversion, in front of ev_in, is what reads it
 };
 struct spx_pipeline {
   std::vector<spx_plan_t> plans;
@@ -160,6 +222,12 @@ static void pipeline_free(spx_pipeline* p) {
     if (S.h_in) (void)hipHostFree(S.h_in);
     if (S.h_out) (void)hipHostFree(S.h_out);
     if (S.h_meta) (void)hipHostFree(S.h_meta);
+    if (S.d_inf) (void)hipFree(S.d_inf);
+    if (S.d_outf) (void)hipFree(S.d_outf);
+    if (S.d_cv) (void)hipFree(S.d_cv);
+    if (S.h_inf) (void)hipHostFree(S.h_inf);
+    if (S.h_outf) (void)hipHostFree(S.h_outf);
+    if (S.h_cv) (void)hipHostFree(S.h_cv);
   }
   if (p->d_tab) (void)hipFree(p->d_tab);
   if (p->s_run) (void)hipStreamDestroy(p->s_run);
@@ -168,6 +236,13 @@ static void pipeline_free(spx_pipeline* p) {
   delete p;
 }
 
+// The int16 calls on a float pipeline, the _float calls on an int16 one: refused before anything is waited for, copied or enqueued.
+static int wrong_kind(const spx_pipeline* p, bool float_call, const char* who) {
+  const bool flt = (p->flags & SPX_PIPELINE_FLOAT) != 0;
+  if (flt == float_call) return 0;
+  return pfail(-1, std::string(who) + (flt ? ": the pipeline was created with SPX_PIPELINE_FLOAT and takes the _float calls only"
+                                           : ": the pipeline was created without SPX_PIPELINE_FLOAT and takes the int16 calls only"));
+}
 static int lane_fail(int lane, const std::string& what) { return pfail(-1, "spx_pipeline: lane " + std::to_string(lane) + ": " + what); }
 // A lane's job by the engine's rules (spx_jobs.h), in the engine's words, with the lane in front
 static int lane_check(const spx_pipeline* p, int lane, const spx_stream_job& j) {
@@ -211,6 +286,7 @@ static int pipeline_build(spx_pipeline* p) {
   PCHK(hipMemcpy(reinterpret_cast<unsigned char*>(p->d_tab) + (size_t)n * 2 * sizeof(int64_t), chans.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
   p->slots.resize((size_t)p->depth);
   const bool host_out = !(p->flags & SPX_PIPELINE_DEVICE_OUT);
+  const bool flt = (p->flags & SPX_PIPELINE_FLOAT) != 0;
   for (auto& S : p->slots) {
     // (d_in: allocated by the first submit of host memory -- a caller whose input is device-resident never needs it)
     PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_out), (p->out_values + 64) * sizeof(int16_t)));
@@ -221,8 +297,20 @@ static int pipeline_build(spx_pipeline* p) {
     PCHK(hipMalloc(&S.ws, p->ws_bytes));
     PCHK(hipMemset(S.ws, 0, p->ws_bytes));
     if (host_out) {
-      PCHK(hipHostMalloc(reinterpret_cast<void**>(&S.h_out), (p->out_values + 64) * sizeof(int16_t), hipHostMallocDefault));
+      if (flt) PCHK(hipHostMalloc(reinterpret_cast<void**>(&S.h_outf), (p->out_values + 64) * sizeof(float), hipHostMallocDefault));
+      else PCHK(hipHostMalloc(reinterpret_cast<void**>(&S.h_out), (p->out_values + 64) * sizeof(int16_t), hipHostMallocDefault));
       PCHK(hipHostMalloc(reinterpret_cast<void**>(&S.h_meta), ((size_t)2 * n + 1) * sizeof(int64_t), hipHostMallocDefault));
+    }
+    if (flt) {
+      // the int16 staging the engine reads, + 64 values as always, zeroed once (the conversion writes the jobs' values only)
+      PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_in), (p->in_values + 64) * sizeof(int16_t)));
+      PCHK(hipMemset(S.d_in, 0, (p->in_values + 64) * sizeof(int16_t)));
+      PCHK(hipHostMalloc(&S.h_cv, spx_conv_table_bytes(n), hipHostMallocDefault));
+      PCHK(hipMalloc(&S.d_cv, spx_conv_table_bytes(n)));
+      if (!host_out) {
+        PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_outf), (p->out_values + 64) * sizeof(float)));
+        PCHK(hipMemset(S.d_outf, 0, (p->out_values + 64) * sizeof(float)));
+      }
     }
     PCHK(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
     PCHK(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming));
@@ -266,6 +354,7 @@ size_t spx_pipeline_input_values(spx_pipeline_t p) { return p ? p->in_values : 0
 
 int16_t* spx_pipeline_host_input(spx_pipeline_t p) {
   if (!p) return nullptr;
+  if (wrong_kind(p, false, "spx_pipeline_host_input")) return nullptr;
   SpxPipeSlot& S = p->slots[(size_t)(p->next_ticket % p->depth)];
   if (!S.h_in) {
     if (hipHostMalloc(reinterpret_cast<void**>(&S.h_in), (p->in_values + 64) * sizeof(int16_t), hipHostMallocDefault) != hipSuccess) {
@@ -277,11 +366,47 @@ int16_t* spx_pipeline_host_input(spx_pipeline_t p) {
   if (S.in_recorded && hipEventSynchronize(S.ev_in) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // the copy that last read it
   return S.h_in;
 }
+float* spx_pipeline_host_input_float(spx_pipeline_t p) {
+  if (!p) return nullptr;
+  if (wrong_kind(p, true, "spx_pipeline_host_input_float")) return nullptr;
+  SpxPipeSlot& S = p->slots[(size_t)(p->next_ticket % p->depth)];
+  if (!S.h_inf) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&S.h_inf), (p->in_values + 16) * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      pfail(-2, "spx_pipeline_host_input_float: pinned allocation failed");
+      return nullptr;
+    }
+  }
+  if (S.in_recorded && hipEventSynchronize(S.ev_in) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // the copy that last read it
+  return S.h_inf;
+}
 
 }  // extern "C"
 
-// One batch with the table `jobs` (the pipeline's own layout in it) and `extent` int16 values of input.
-static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, size_t extent, const int16_t* in, int in_is_device) {
+// SPX_PIPELINE_FLOAT: what a submit enqueues on the copy stream in place of the int16 copy -- the copy of a host input into the float
+// staging, this batch's conversion table, the conversion into the int16 staging -- with ev_in recorded behind the conversion.
+static int pipeline_float_input(spx_pipeline_t p, SpxPipeSlot& S, size_t extent, const float* in, int in_is_device, int* max_out) {
+  // (the slot's pinned table was last read by a kernel in front of an ev_in that the batch behind ev_done waited for: free to rewrite)
+  int max_in = 1;
+  if (spx_conv_table_fill(S.h_cv, S.jobs.data(), p->n, &max_in, max_out)) return pfail(-1, "spx_pipeline: a lane too large for one conversion launch");
+  const float* src = in;
+  if (!in_is_device) {
+    if (!S.d_inf) PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_inf), (p->in_values + 16) * sizeof(float)));   // (+ 16: never empty)
+    if (extent) PCHK(hipMemcpyAsync(S.d_inf, in, extent * sizeof(float), hipMemcpyHostToDevice, p->s_h2d));
+    src = S.d_inf;
+  }
+  spx_conv_table_upload(S.h_cv, S.d_cv, p->n, p->s_h2d);
+  spx_conv_launch_in(S.d_cv, p->n, max_in, src, S.d_in, p->s_h2d);
+  PCHK(hipEventRecord(S.ev_in, p->s_h2d));
+  S.in_recorded = true;
+  return 0;
+}
+
+// One batch with the table `jobs` (the pipeline's own layout in it) and `extent` values of input: int16, or float on a pipeline
+// created with SPX_PIPELINE_FLOAT.
+static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, size_t extent, const void* in_any, int in_is_device) {
+  const bool flt = (p->flags & SPX_PIPELINE_FLOAT) != 0;
+  const int16_t* in = flt ? nullptr : static_cast<const int16_t*>(in_any);
   const int64_t ticket = p->next_ticket;
   SpxPipeSlot& S = p->slots[(size_t)(ticket % p->depth)];
   // at most `depth` batches in flight: the batch that last used this buffer set has finished (its output, if nobody asked for
@@ -290,7 +415,13 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, siz
   S.jobs.assign(jobs, jobs + p->n);
   const int16_t* dev_in = in;
   void* in_ready = nullptr;
-  if (!in_is_device) {
+  int cv_max_out = 1;
+  if (flt) {
+    const int frc = pipeline_float_input(p, S, extent, static_cast<const float*>(in_any), in_is_device, &cv_max_out);
+    if (frc) { (void)hipDeviceSynchronize(); (void)hipGetLastError(); S.ticket = -1; return frc; }
+    dev_in = S.d_in;
+    in_ready = S.ev_in;
+  } else if (!in_is_device) {
     // (the kernels that last read d_in are behind ev_done, waited for above: the copy may start at once)
     // ONE copy stream: with two taking turns -- so that the next 82 MB copy starts while the previous one still runs and the
     // 50 - 80 us between two chained copies go -- the leg read 1.73 - 1.75 ms per batch against 1.67 (profiles/r05/r5o_copy_streams.txt).
@@ -311,16 +442,19 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, siz
   const bool host_out = !(p->flags & SPX_PIPELINE_DEVICE_OUT);
   // With the outputs left on the device nothing of a batch has to run behind its walk kernel: the call is DETACHED from the run
   // stream (spx_engine.hip SpxCallOpts) -- the batch's event is recorded on the walk stream itself and the run stream stays empty.
+  // (SPX_PIPELINE_FLOAT | SPX_PIPELINE_DEVICE_OUT: the output conversion runs behind the walk kernel on the run stream, so the call
+  // cannot be detached from it and takes the order the host-output pipeline takes)
   bool event_recorded = false;
+  const bool detach = !host_out && !flt;
   if (p->mixed) {
     // (round 6: detached like a one-plan batch -- the groups' walk kernels on the library's walk streams, two calls' worth in flight)
     rc = spx_internal_run_mixed(p->plans.data(), (int)p->plans.size(), S.jobs.data(), p->plan_index.data(), p->n, dev_in, S.d_out, S.d_nout,
-                                S.ws, p->ws_bytes, p->s_run, true, in_ready, host_out ? nullptr : S.ev_done, !host_out);
-    event_recorded = !host_out;
+                                S.ws, p->ws_bytes, p->s_run, true, in_ready, detach ? S.ev_done : nullptr, detach);
+    event_recorded = detach;
   } else {
     rc = spx_internal_run(p->plans[0], S.jobs.data(), p->n, dev_in, S.d_out, S.d_nout, S.ws, p->ws_bytes, nullptr, p->s_run, true, true, in_ready,
-                          host_out ? nullptr : S.ev_done, !host_out);
-    event_recorded = !host_out;
+                          detach ? S.ev_done : nullptr, detach);
+    event_recorded = detach;
   }
   if (rc) {
     // part of the batch may have been enqueued on this buffer set: nothing of it is handed out, and nothing is left in flight
@@ -329,7 +463,7 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, siz
     S.ticket = -1;
     return rc;
   }
-  S.in_host = !in_is_device;
+  S.in_host = flt || !in_is_device;   // (a float input of either kind is consumed by its conversion, in front of ev_in)
   if (host_out) {
     const int n = p->n;
     const int64_t* d_off = p->d_tab;
@@ -337,7 +471,13 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, siz
     const int* d_ch = reinterpret_cast<const int*>(p->d_tab + 2 * (size_t)n);
     hipLaunchKernelGGL(spx_pipe_offsets_kernel, dim3(1), dim3(256), 0, p->s_run, S.d_nout, d_ch, d_cap, n, S.d_offsets, S.h_meta, S.h_meta + n + 1);
     const int wgs = n < p->pack_wgs ? n : p->pack_wgs;
-    hipLaunchKernelGGL(spx_pipe_copy_kernel, dim3(wgs), dim3(256), 0, p->s_run, S.d_out, d_off, S.d_offsets, n, S.h_out);
+    if (flt) hipLaunchKernelGGL(spx_pipe_copy_float_kernel, dim3(wgs), dim3(256), 0, p->s_run, S.d_out, d_off, S.d_offsets, n, S.h_outf);
+    else hipLaunchKernelGGL(spx_pipe_copy_kernel, dim3(wgs), dim3(256), 0, p->s_run, S.d_out, d_off, S.d_offsets, n, S.h_out);
+  } else if (flt) {
+    // (the table went to the device on the copy stream in front of ev_in, which every kernel of the batch is behind; said once more
+    // for the run stream, whatever order the engine chose)
+    PCHK(hipStreamWaitEvent(p->s_run, S.ev_in, 0));
+    spx_conv_launch_out(S.d_cv, p->n, cv_max_out, S.d_nout, S.d_out, S.d_outf, p->s_run);
   }
   if (!event_recorded) PCHK(hipEventRecord(S.ev_done, p->s_run));
   PCHK(hipGetLastError());
@@ -402,7 +542,17 @@ extern "C" {
 
 int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_device) {
   if (!p || !in) return pfail(-1, "spx_pipeline_submit: bad arguments");
-  if (pipeline_current(p, "spx_pipeline_submit")) return -1;
+  if (wrong_kind(p, false, "spx_pipeline_submit") || pipeline_current(p, "spx_pipeline_submit")) return -1;
+  return pipeline_submit(p, p->jobs.data(), p->in_values, in, in_is_device);
+}
+static int float_aligned(const float* in, const char* who) {
+  if (reinterpret_cast<uintptr_t>(in) & 3) return pfail(-1, std::string(who) + ": in must be 4-byte aligned");
+  return 0;
+}
+int64_t spx_pipeline_submit_float(spx_pipeline_t p, const float* in, int in_is_device) {
+  if (!p || !in) return pfail(-1, "spx_pipeline_submit_float: bad arguments");
+  if (wrong_kind(p, true, "spx_pipeline_submit_float") || float_aligned(in, "spx_pipeline_submit_float") ||
+      pipeline_current(p, "spx_pipeline_submit_float")) return -1;
   return pipeline_submit(p, p->jobs.data(), p->in_values, in, in_is_device);
 }
 int spx_pipeline_jobs_fit(spx_pipeline_t p, const spx_stream_job* jobs) {
@@ -413,10 +563,19 @@ int spx_pipeline_jobs_fit(spx_pipeline_t p, const spx_stream_job* jobs) {
 }
 int64_t spx_pipeline_submit_jobs(spx_pipeline_t p, const spx_stream_job* jobs, const int16_t* in, int in_is_device) {
   if (!p || !jobs || !in) return pfail(-1, "spx_pipeline_submit_jobs: bad arguments");
-  if (pipeline_current(p, "spx_pipeline_submit_jobs")) return -1;
+  if (wrong_kind(p, false, "spx_pipeline_submit_jobs") || pipeline_current(p, "spx_pipeline_submit_jobs")) return -1;
   std::vector<spx_stream_job> table;
   size_t extent = 0;
   if (pipeline_check(p, jobs, table, &extent)) return -1;   // (before anything is waited for, copied or enqueued: no ticket is used up)
+  return pipeline_submit(p, table.data(), extent, in, in_is_device);
+}
+int64_t spx_pipeline_submit_jobs_float(spx_pipeline_t p, const spx_stream_job* jobs, const float* in, int in_is_device) {
+  if (!p || !jobs || !in) return pfail(-1, "spx_pipeline_submit_jobs_float: bad arguments");
+  if (wrong_kind(p, true, "spx_pipeline_submit_jobs_float") || float_aligned(in, "spx_pipeline_submit_jobs_float") ||
+      pipeline_current(p, "spx_pipeline_submit_jobs_float")) return -1;
+  std::vector<spx_stream_job> table;
+  size_t extent = 0;
+  if (pipeline_check(p, jobs, table, &extent)) return -1;
   return pipeline_submit(p, table.data(), extent, in, in_is_device);
 }
 
@@ -428,17 +587,31 @@ static SpxPipeSlot* slot_of(spx_pipeline_t p, int64_t ticket) {
 int spx_pipeline_input_consumed(spx_pipeline_t p, int64_t ticket) {
   SpxPipeSlot* S = slot_of(p, ticket);
   if (!S) return pfail(-1, "spx_pipeline_input_consumed: unknown ticket, or its buffers have been handed to a later batch");
-  // host input: the copy in has read it; device input: the kernels read it until the batch is done (the walk kernel copies from it)
+  // host input: the copy in has read it; device input: the kernels read it until the batch is done (the walk kernel copies from it);
+  // a float input of either kind: its conversion, in front of ev_in, has read it (in_host is set for both)
   if (S->in_host) PCHK(hipEventSynchronize(S->ev_in));
   else PCHK(hipEventSynchronize(S->ev_done));
   return 0;
 }
 int spx_pipeline_wait(spx_pipeline_t p, int64_t ticket, const int16_t** out, const int64_t** offsets, const int64_t** counts) {
+  if (p && wrong_kind(p, false, "spx_pipeline_wait")) return -1;
   SpxPipeSlot* S = slot_of(p, ticket);
   if (!S) return pfail(-1, "spx_pipeline_wait: unknown ticket, or its buffers have been handed to a later batch");
   PCHK(hipEventSynchronize(S->ev_done));
   const bool host_out = !(p->flags & SPX_PIPELINE_DEVICE_OUT);
   if (out) *out = host_out ? S->h_out : S->d_out;
+  if (offsets) *offsets = host_out ? S->h_meta : p->static_offsets.data();
+  if (counts) *counts = host_out ? S->h_meta + p->n + 1 : S->d_nout;
+  return 0;
+}
+
+int spx_pipeline_wait_float(spx_pipeline_t p, int64_t ticket, const float** out, const int64_t** offsets, const int64_t** counts) {
+  if (p && wrong_kind(p, true, "spx_pipeline_wait_float")) return -1;
+  SpxPipeSlot* S = slot_of(p, ticket);
+  if (!S) return pfail(-1, "spx_pipeline_wait_float: unknown ticket, or its buffers have been handed to a later batch");
+  PCHK(hipEventSynchronize(S->ev_done));
+  const bool host_out = !(p->flags & SPX_PIPELINE_DEVICE_OUT);
+  if (out) *out = host_out ? S->h_outf : S->d_outf;
   if (offsets) *offsets = host_out ? S->h_meta : p->static_offsets.data();
   if (counts) *counts = host_out ? S->h_meta + p->n + 1 : S->d_nout;
   return 0;
