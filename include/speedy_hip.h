@@ -409,6 +409,19 @@ long long spx_debug_xfade_check(int n_lo, int n_hi);
  * `per_thread` pseudo-random operands of the ranges the kernel feeds them; the number of results that differ from the IEEE
  * sequences' (0 is the only acceptable answer), -1 on a runtime error. */
 long long spx_debug_arith_check(unsigned seed, unsigned threads, unsigned per_thread);
+/* The walk kernels' lag selectors on sums the caller supplies (all pointers HOST): the arg-min of d / lag over lags p0 .. p0 + n_lags
+ * - 1, first lag among equal ratios, as the kernels compute it -- one wave per vector.
+ * spx_debug_select_check: the speed-up kernel's selector, one lag per lane (n_lags <= 64, rows of 64 words) or two (n_lags <= 128, rows
+ * of 128 words); ties of the integer key are rescanned exactly where max_period^2 >= 65536, as in the kernel.  lag_index[v] = the winner's
+ * index, kmin[v] = floor(d 2^16 / lag) of the winner.
+ * spx_debug_select_fold_check: the general kernel's selector, folded 64 lags at a time (rows of n_lags rounded up to a multiple of 64
+ * words, p0 >= 10); want_max: the arg-max as well; fresh: the first fold in the form that takes its first candidate without a
+ * comparison.  out3[3 v ..] = best lag, minDiff, maxDiff (the floor quotients; maxDiff = 0 without want_max).
+ * Every word of a row is read: the lanes beyond n_lags may hold anything.  Return 0; -1 on a bad argument, on a sum above 65535 lag in a
+ * valid lane (checked on the host before anything is launched) or on a runtime error. */
+int spx_debug_select_check(const unsigned* d, int n_vectors, int p0, int n_lags, int max_period, int two_per_lane, int* lag_index,
+                           unsigned* kmin);
+int spx_debug_select_fold_check(const unsigned* d, int n_vectors, int p0, int n_lags, int want_max, int fresh, int* out3);
 /* The analysis kernel's natural log ("log spec v2", DESIGN.md 4a: its argument is always a float quotient, speedy.c:716-717) over
  * EVERY positive normal float: block b = the 2^20 float patterns b << 20 ..; sums[b] (HOST uint64[2040], blocks 8 .. 2039 filled) =
  * the sum of the results' bit patterns modulo 2^64.  The oracle computes the same sums (oracle/orc_logcheck.c): equal sums, block

@@ -31,6 +31,7 @@
 #define SPX_WCH 64   // frames in the first walk chunk when the analysis kernel runs concurrently (multiple of the tile)
 
 #include "spx_walk_common.h"
+#include "spx_select.h"
 
 // Diagnostic build only (-DSPX_STAMPS): per-phase shader-cycle sums of workgroup 0, lane 0.  Never in the product.
 #ifdef SPX_STAMPS
@@ -216,61 +217,7 @@ __device__ __forceinline__ void ensure_window(WalkCtx& X, pos_t pos, int need) {
   }
 }
 
-// Running result of the dependency's sequential arg-min / arg-max scan over lags.
-struct Sel {
-  unsigned bestD, worstD;
-  int bestP, worstP;
-};
-
-// Fold the 64 lanes' (d, p) candidates (lane order = ascending lag) into the running result, exactly as a
-// sequential scan would: float ratios, DPP wave min/max, then an exact integer resolve on the scalar unit of the
-// lanes within 2^-16 of the extremum (strict compare, so the FIRST lag wins ties).  Wave-uniform result.
-template <bool WANT_MAX, bool FRESH = false>
-__device__ __forceinline__ void select_fold(Sel& S, unsigned d, int p0, bool valid) {
-  const int lane = threadIdx.x & 63;
-  const float r = (float)d * __builtin_amdgcn_rcpf((float)(p0 + lane));  // within 2^-21 of d/p
-  const float rmin = wave_min_f(valid ? r : __builtin_huge_valf());
-  unsigned long long mmin = __builtin_amdgcn_ballot_w64(valid && r <= rmin * 1.0000153f);  // 1 + 2^-16
-  if (FRESH) {  // S is empty and some lane is valid: the first candidate is taken without a comparison
-    const int i = __builtin_ctzll(mmin);
-    mmin &= mmin - 1;
-    S.bestD = (unsigned)__builtin_amdgcn_readlane((int)d, i);
-    S.bestP = p0 + i;
-  }
-  while (mmin) {
-    const int i = __builtin_ctzll(mmin);
-    mmin &= mmin - 1;
-    const unsigned di = (unsigned)__builtin_amdgcn_readlane((int)d, i);
-    const int pi = p0 + i;
-    if (S.bestP == 0 || (unsigned long long)di * (unsigned)S.bestP < (unsigned long long)S.bestD * (unsigned)pi) {
-      S.bestD = di;
-      S.bestP = pi;
-    }
-  }
-  if (WANT_MAX) {
-    const float rmax = wave_max_f(valid ? r : 0.0f);
-    unsigned long long mmax = __builtin_amdgcn_ballot_w64(valid && r >= rmax * 0.9999847f);
-    while (mmax) {
-      const int i = __builtin_ctzll(mmax);
-      mmax &= mmax - 1;
-      const unsigned di = (unsigned)__builtin_amdgcn_readlane((int)d, i);
-      const int pi = p0 + i;
-      if (S.worstP == 0 ||
-          (unsigned long long)di * (unsigned)S.worstP > (unsigned long long)S.worstD * (unsigned)pi) {
-        S.worstD = di;
-        S.worstP = pi;
-      }
-    }
-  }
-}
-__device__ __forceinline__ void select_finish(const Sel& S, int* retBest, int* retMin, int* retMax) {
-  // the scan's initial (maxDiff = 0, worstPeriod = 255) survives unless some lag has diff > 0
-  const unsigned worstD = S.worstD;
-  const int worstP = (worstD == 0) ? 255 : S.worstP;
-  *retBest = uni(S.bestP);
-  *retMin = uni((int)udiv_small(S.bestD, (unsigned)S.bestP));
-  *retMax = uni((int)udiv_small(worstD, (unsigned)worstP));
-}
+// (Sel, select_fold, select_finish -- the running arg-min / arg-max over lags -- live in spx_select.h: the selector check includes them too.)
 
 // One lane per lag, the whole sum in the lane (no cross-lane traffic): used for the coarse search, which every
 // wave runs redundantly.  A0/A1: dword views of the signal array and of its copy shifted by one sample; o = offset

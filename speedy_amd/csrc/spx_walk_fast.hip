@@ -42,6 +42,7 @@
 #include <stdlib.h>
 
 #include "spx_walk_common.h"
+#include "spx_select.h"
 
 #ifndef SPX_WALK_PRIO
 #define SPX_WALK_PRIO 3  // the search waves are the latency-critical chain: they issue first where another kernel shares a SIMD
@@ -162,11 +163,6 @@ __device__ __forceinline__ int lds_probe(const int* p) {
 }
 
 __device__ __forceinline__ void fast_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-  SPX_WAVE_REDUCE("v_min_u32_dpp", v);
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
 
 // (The cross-fade's quotient -- xfade_rcp, xfade_quot -- lives in spx_walk_common.h: the general walk kernel uses it too.)
 // Its numerator d (n - t) + u t as two 24-bit multiplications (|d|, |u| <= 2^15, n <= 2^12):
@@ -529,58 +525,7 @@ __device__ __forceinline__ void fast_refill(const FastOut& X, const FastLds& LY,
   fast_sync();
 }
 
-// arg-min over the lanes of diff/lag (first lag wins ties, as the dependency's sequential scan).  Returns the lane.
-__device__ __forceinline__ int fast_select(unsigned dsum, double scale, bool valid, bool needResolve, int p0,
-                                           unsigned& kmin) {
-  const double q = __builtin_fma((double)dsum, scale, 0x1p-12);  // floor(dsum * 65536 / p) + frac; exact (header comment)
-  const unsigned key = valid ? (unsigned)q : 0xffffffffu;
-  kmin = wave_min_u32(key);
-  unsigned long long m = __builtin_amdgcn_ballot_w64(key == kmin);
-  int idx = __builtin_ctzll(m);
-  m &= m - 1;
-  if (needResolve && m) {  // lag products can exceed 2^16: equal keys need not be equal ratios -- exact scan of the ties
-    unsigned bd = (unsigned)__builtin_amdgcn_readlane((int)dsum, idx);
-    int bp = p0 + idx;
-    while (m) {
-      const int i = __builtin_ctzll(m);
-      m &= m - 1;
-      const unsigned di = (unsigned)__builtin_amdgcn_readlane((int)dsum, i);
-      const int pi = p0 + i;
-      if ((unsigned long long)di * (unsigned)bp < (unsigned long long)bd * (unsigned)pi) { bd = di; bp = pi; idx = i; }
-    }
-  }
-  return idx;
-}
-
-// The same over two lags per lane (lags lane and 64 + lane; refine searches of more than 64 lags).  Returns the lag index.
-__device__ __forceinline__ int fast_select2(unsigned dsum, unsigned dsum2, double scale, double scale2, bool valid, bool valid2,
-                                            bool needResolve, int p0, unsigned& kmin) {
-  const double q = __builtin_fma((double)dsum, scale, 0x1p-12), q2 = __builtin_fma((double)dsum2, scale2, 0x1p-12);
-  const unsigned key = valid ? (unsigned)q : 0xffffffffu, key2 = valid2 ? (unsigned)q2 : 0xffffffffu;
-  kmin = wave_min_u32(key < key2 ? key : key2);
-  unsigned long long m = __builtin_amdgcn_ballot_w64(key == kmin), m2 = __builtin_amdgcn_ballot_w64(key2 == kmin);
-  int idx = m ? __builtin_ctzll(m) : 64 + __builtin_ctzll(m2);
-  if (m) m &= m - 1; else m2 &= m2 - 1;
-  if (needResolve && (m | m2)) {  // exact scan of the ties, in lag order
-    unsigned bd = idx < 64 ? (unsigned)__builtin_amdgcn_readlane((int)dsum, idx) : (unsigned)__builtin_amdgcn_readlane((int)dsum2, idx - 64);
-    int bp = p0 + idx;
-    while (m) {
-      const int i = __builtin_ctzll(m);
-      m &= m - 1;
-      const unsigned di = (unsigned)__builtin_amdgcn_readlane((int)dsum, i);
-      const int pi = p0 + i;
-      if ((unsigned long long)di * (unsigned)bp < (unsigned long long)bd * (unsigned)pi) { bd = di; bp = pi; idx = i; }
-    }
-    while (m2) {
-      const int i = __builtin_ctzll(m2);
-      m2 &= m2 - 1;
-      const unsigned di = (unsigned)__builtin_amdgcn_readlane((int)dsum2, i);
-      const int pi = p0 + 64 + i;
-      if ((unsigned long long)di * (unsigned)bp < (unsigned long long)bd * (unsigned)pi) { bd = di; bp = pi; idx = 64 + i; }
-    }
-  }
-  return idx;
-}
+// (fast_select, fast_select2 -- the arg-min of diff/lag over the lanes -- live in spx_select.h: the selector check includes them too.)
 
 // lane `LANE` of `old` replaced by the wave-uniform value v (v_writelane_b32: no EXEC change)
 template <typename T>
