@@ -107,8 +107,8 @@ int spx_batch_run(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, co
  * stage lies behind everything they observe); spx_batch_pack_outputs and spx_batch_read_steps work on the result unchanged.
  * A rate <= 0, not finite, or so large that (int)(sample rate / rate) < 1 is refused: -1, spx_last_error, nothing launched.
  * The workspace (spx_batch_workspace_bytes_rate) also holds the speed stage's output of the jobs with a rate other than 1.
- * Asynchronous on hip_stream like spx_batch_run, kernels in sequence; the plain call only (no _ahead / _overlapped / _mixed form,
- * no pipeline object).  Any channel count the walk kernel's window takes: the 16 of the streaming API's rate
+ * Asynchronous on hip_stream like spx_batch_run, kernels in sequence; the plain call only (no _ahead / _overlapped / _mixed form).
+ * The pipeline object takes a rate per lane and per batch: spx_pipeline_create_rate below.  Any channel count the walk kernel's window takes: the 16 of the streaming API's rate
  * stage do not apply. */
 int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, const int16_t* in,
                        int16_t* out, int64_t* n_out, void* workspace, size_t workspace_bytes,
@@ -306,13 +306,61 @@ int spx_pipeline_wait(spx_pipeline_t p, int64_t ticket, const int16_t** out, con
  * WRONG-KIND CALLS -- spx_pipeline_submit, _submit_jobs, _wait, _host_input on a float pipeline; the _float calls on an int16 one --
  * return -1 (NULL) with a message that names the flag, before anything is waited for, copied or enqueued: no ticket is used up and
  * the pipeline stays fully usable.  A float pointer that is not 4-byte aligned is refused the same way.
- * STILL OUT OF SCOPE: playback rates in the pipeline, float _ahead / _overlapped / _mixed* calls on caller-owned buffers, a float
- * spx_batch_pack_outputs. */
+ * Playback rates on float samples: spx_pipeline_create_rate with the flag and spx_pipeline_submit_jobs_rate_float, further down.
+ * STILL OUT OF SCOPE: float _ahead / _overlapped / _mixed* calls on caller-owned buffers, a float spx_batch_pack_outputs. */
 /* Pinned host staging of spx_pipeline_input_values() floats for the next submit, as spx_pipeline_host_input. */
 float* spx_pipeline_host_input_float(spx_pipeline_t p);
 int64_t spx_pipeline_submit_float(spx_pipeline_t p, const float* in, int in_is_device);
 int64_t spx_pipeline_submit_jobs_float(spx_pipeline_t p, const spx_stream_job* jobs, const float* in, int in_is_device);
 int spx_pipeline_wait_float(spx_pipeline_t p, int64_t ticket, const float** out, const int64_t** offsets, const int64_t** counts);
+
+/* ---- the RATE PIPELINE: a playback rate per lane and per batch (sonicSetRate before the first write, sonic2.h:70) ----
+ * A one-plan pipeline whose lanes each carry a playback rate, which may differ from batch to batch as the job table may.  A lane's
+ * output is byte for byte what spx_batch_run_rate gives the same job, rate and samples (on float samples: spx_batch_run_float).
+ * CREATION  spx_pipeline_create with one more table:
+ *   rates   HOST float[n_streams]: the rate each lane is SIZED FOR; NULL = every rate 1, as in spx_batch_run_rate
+ *   flags   SPX_PIPELINE_DEVICE_OUT and SPX_PIPELINE_FLOAT, in any combination
+ * A lane's capacity, in FINAL frames (behind the rate stage), is spx_plan_out_capacity_rate(plan, n_in, speed, nonlinear, rate); the
+ * output layout is every pipeline's (regions at multiples of 32 values).  The workspace is sized so that EVERY lane can resample,
+ * the lanes created at rate 1 included: it reserves the speed stage's staging of all its lanes, and a lane created at rate 1 takes
+ * rate 2 in the next batch.  NULL with spx_last_error, "spx_pipeline: lane N: " and the rule, for a job spx_batch_run refuses or a
+ * rate spx_batch_run_rate refuses (not finite, <= 0, (int)(sample rate / rate) < 1).  There is no mixed-sample-rate form, as
+ * spx_batch_run_rate has none.
+ * FIT  spx_pipeline_jobs_fit_rate, which both submit calls below apply before anything is waited for, copied or enqueued.  A table
+ * with its rates (NULL = every rate 1) is accepted if and only if
+ *   - every rule of spx_pipeline_jobs_fit holds (channels, the engine's job rules, the input's extent), its capacity rule in final
+ *     frames:  spx_plan_out_capacity_rate(plan, n_in, speed, nonlinear, rates[i]) <= the lane's capacity at creation,
+ *   - every rate is one spx_batch_run_rate takes,
+ *   - spx_batch_workspace_bytes_rate of the table with these rates <= the pipeline's workspace.
+ * A refusal returns -1 and names the lane and the limit -- the rate itself, the capacity in final frames with both numbers, or the
+ * workspace -- uses up no ticket and leaves the batches in flight untouched.  The rule is the inequality, not "rate >= the creation
+ * rate": the rate stage works with both sample rates halved until they fit 14 bits, so the capacity is not promised monotone in the
+ * rate.  SIZING, as advice: create a lane with the longest n_in, the smallest speed if below 1, and the smallest rate it will see.
+ * THE OTHER CALLS on a rate pipeline: spx_pipeline_submit / _submit_float run the creation table at the creation rates;
+ * spx_pipeline_submit_jobs / _submit_jobs_float / _jobs_fit mean "every rate 1" (the _rate call with rates == NULL); wait,
+ * wait_float, input_consumed, host_input(_float), input_values and depth are unchanged, and so is the int16 / float wrong-kind rule.
+ * Offsets and counts are in final frames and values, offsets multiples of 32, an empty lane takes no room; with
+ * SPX_PIPELINE_DEVICE_OUT the offsets are the static layout and the counts are in device memory.
+ * The three _rate calls on a pipeline NOT made by spx_pipeline_create_rate return -1 with a message that names
+ * spx_pipeline_create_rate, before anything is waited for or enqueued; spx_pipeline_create / _create_mixed are what they were.
+ * WHAT A SUBMIT ENQUEUES  A batch whose rates are all 1 is an ordinary pipeline batch: the overlapped order (detached where an
+ * ordinary batch is), and the bytes, counts and offsets of a pipeline made by spx_pipeline_create from the same table.  A batch with
+ * at least one rate other than 1: the copy stream does what it always does (copy in, on float samples the conversion); then, on the
+ * run stream and behind the input, the engine runs the batch AS spx_batch_run_rate RUNS IT -- analysis, tension, the general walk
+ * kernel without flush truncation into the speed-stage staging of the slot's workspace, the rate kernel into the slot's output,
+ * kernels in sequence, rate-1 lanes bypassed as in the batch call -- and behind it the gather (or the float conversion) every batch
+ * ends with.  Such a batch is never detached.  Batches of both kinds alternate freely on one pipeline.
+ * COST, plainly: a rate batch costs about what spx_batch_run_rate costs -- 4.86 ms of kernels for 256 x 10 s against 1.73 ms for the
+ * plain call (profiles/batch_rate.txt): the general walk kernel, and no overlap between the kernels of consecutive rate batches.
+ * What the pipeline adds is what it owns: buffers, layout, packing, and copies in that run beside the neighbours' kernels
+ * (profiles/pipeline_rate.txt has the measurement against the loop around spx_batch_run_rate that a caller had to write before). */
+spx_pipeline_t spx_pipeline_create_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, int depth,
+                                        unsigned flags);
+int spx_pipeline_jobs_fit_rate(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates);
+int64_t spx_pipeline_submit_jobs_rate(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates, const int16_t* in,
+                                      int in_is_device);
+int64_t spx_pipeline_submit_jobs_rate_float(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates, const float* in,
+                                            int in_is_device);
 
 /* Pinned host memory for callers without HIP headers (the input of spx_pipeline_submit at the full link rate). */
 void* spx_host_alloc(size_t bytes);

@@ -107,6 +107,10 @@ SYMBOLS = {
     "spx_pipeline_submit_float": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int]),
     "spx_pipeline_submit_jobs_float": (C.c_int64, [C.c_void_p, C.POINTER(StreamJob), C.c_void_p, C.c_int]),
     "spx_pipeline_wait_float": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "spx_pipeline_create_rate": (C.c_void_p, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_int, C.c_int, C.c_uint]),
+    "spx_pipeline_jobs_fit_rate": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), c_float_p]),
+    "spx_pipeline_submit_jobs_rate": (C.c_int64, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_void_p, C.c_int]),
+    "spx_pipeline_submit_jobs_rate_float": (C.c_int64, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_void_p, C.c_int]),
     "spx_host_alloc": (C.c_void_p, [C.c_size_t]),
     "spx_host_free": (None, [C.c_void_p]),
     "spx_device_alloc": (C.c_void_p, [C.c_size_t]),

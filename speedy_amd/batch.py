@@ -474,11 +474,16 @@ class Pipeline:
     float_samples: a pipeline on FLOAT samples in (-1, 1) (SPX_PIPELINE_FLOAT): pack, host_input, submit, submit_jobs, wait and
     results work on float32 -- numpy arrays, pinned torch tensors, CUDA tensors -- with both conversions on the GPU, by FloatBatch's
     rules (the input scale per lane by the nonlinear factor of the batch's job, every output value an int16 / 32767.0f).  A CUDA
-    tensor needs numel() >= the batch's extent only: no padding."""
+    tensor needs numel() >= the batch's extent only: no padding.
+
+    rate: a RATE pipeline (spx_pipeline_create_rate; one plan only): the playback rate (sonicSetRate) every lane is sized for, one
+    value or one per lane.  submit() runs the creation table at these rates; table / fits / submit_jobs take rate= for THIS batch
+    (None = every rate 1), and a lane takes any rate whose capacity in final frames (Plan.out_capacity(..., rate=)) fits the lane's --
+    create a lane with the smallest rate it will see.  Outputs are Batch(..., rate=)'s, byte for byte."""
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, depth=0, device_out=False, plan_index=None,
-                 float_samples=False):
-        if float_samples and not torch.cuda.is_available():
+                 float_samples=False, rate=None):
+        if (float_samples or rate is not None) and not torch.cuda.is_available():
             raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
         self.float_samples = bool(float_samples)
         self._np_dt, self._torch_dt, self._c_dt = ((np.float32, torch.float32, C.c_float) if float_samples else
@@ -506,7 +511,14 @@ class Pipeline:
         self.total_in = in_off
         self.device_out = bool(device_out)
         flags = (1 if device_out else 0) | (2 if float_samples else 0)   # SPX_PIPELINE_DEVICE_OUT | SPX_PIPELINE_FLOAT
-        if plan_index is None and len(plans) == 1:
+        self.rates = None
+        if rate is not None:
+            if plan_index is not None or len(plans) != 1:
+                raise ValueError("a rate pipeline has one plan (spx_pipeline_create_rate has no mixed-sample-rate form)")
+            self.rates = np.ascontiguousarray(np.broadcast_to(np.asarray(rate, np.float32), (n,)))
+            self.h = self.L.spx_pipeline_create_rate(plans[0].h, self.jobs, self.rates.ctypes.data_as(C.POINTER(C.c_float)), n,
+                                                     int(depth), flags)
+        elif plan_index is None and len(plans) == 1:
             self.h = self.L.spx_pipeline_create(plans[0].h, self.jobs, n, int(depth), flags)
         else:
             self._pidx = (C.c_int * n)(*[int(v) for v in (plan_index if plan_index is not None else [0] * n)])
@@ -561,8 +573,20 @@ class Pipeline:
         call = self.L.spx_pipeline_submit_float if self.float_samples else self.L.spx_pipeline_submit
         return self._ticket(call(self.h, ptr, 1 if device else 0), x, "spx_pipeline_submit")
 
-    def table(self, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None):
-        """The job table of one batch (spx_stream_job[n], host): None = the value the lane was created with."""
+    def _rates(self, rate):
+        """This batch's rates as (float32 array kept alive by the caller, pointer), or (None, None)."""
+        if rate is None:
+            return None, None
+        if self.rates is None:
+            raise RuntimeError("the pipeline takes no playback rates: create it with rate= (spx_pipeline_create_rate)")
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rate, np.float32), (self.n,)))
+        return r, r.ctypes.data_as(C.POINTER(C.c_float))
+
+    def table(self, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None, rate=None):
+        """The job table of one batch (spx_stream_job[n], host): None = the value the lane was created with.  With rate= (a rate
+        pipeline): the pair (table, float32 rates) the _rate calls take."""
+        if rate is not None:
+            return self.table(lengths, speed, nonlinear, feedback, in_offs), self._rates(rate)[0]
         n = self.n
         assert len(lengths) == n
         sp = self.speeds if speed is None else np.broadcast_to(np.asarray(speed, np.float32), (n,))
@@ -576,19 +600,28 @@ class Pipeline:
             j.channels, j.speed, j.nonlinear, j.feedback = int(self.channels[i]), float(sp[i]), float(nlv[i]), float(fb[i])
         return jobs
 
-    def fits(self, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None):
-        """Would submit_jobs accept this batch?  (spx_pipeline_jobs_fit: enqueues nothing, waits for nothing.)"""
-        return self.L.spx_pipeline_jobs_fit(self.h, self.table(lengths, speed, nonlinear, feedback, in_offs)) == 0
+    def fits(self, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None, rate=None):
+        """Would submit_jobs accept this batch?  (spx_pipeline_jobs_fit / _fit_rate: enqueues nothing, waits for nothing.)"""
+        jobs = self.table(lengths, speed, nonlinear, feedback, in_offs)
+        if rate is None:
+            return self.L.spx_pipeline_jobs_fit(self.h, jobs) == 0
+        _keep, rp = self._rates(rate)
+        return self.L.spx_pipeline_jobs_fit_rate(self.h, jobs, rp) == 0
 
-    def submit_jobs(self, x, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None, device=False):
+    def submit_jobs(self, x, lengths, speed=None, nonlinear=None, feedback=None, in_offs=None, device=False, rate=None):
         """submit() with THIS batch's lengths, speeds, nonlinear factors, feedback strengths and input offsets per lane (None = the
-        creation value).  A host input need only reach this batch's extent: max over lanes of in_off + length * channels.
+        creation value) -- and, on a rate pipeline, playback rates (rate=: one value or one per lane; None = every rate 1).
+        A host input need only reach this batch's extent: max over lanes of in_off + length * channels.
         RuntimeError with the library's text (the lane and the limit) for a batch that does not fit the pipeline."""
         jobs = self.table(lengths, speed, nonlinear, feedback, in_offs)
         # (at most the pipeline's input: a table that ends behind it is the library's to refuse, not an assertion's)
         extent = min(self.total_in, max(int(j.in_off) + int(j.n_in) * int(j.channels) for j in jobs))
         x, ptr, dev = self._input_ptr(x, extent)
         device = dev if isinstance(x, torch.Tensor) else device
+        if rate is not None:
+            _keep, rp = self._rates(rate)   # (read before the call returns)
+            call = self.L.spx_pipeline_submit_jobs_rate_float if self.float_samples else self.L.spx_pipeline_submit_jobs_rate
+            return self._ticket(call(self.h, jobs, rp, ptr, 1 if device else 0), x, "spx_pipeline_submit_jobs_rate")
         call = self.L.spx_pipeline_submit_jobs_float if self.float_samples else self.L.spx_pipeline_submit_jobs
         return self._ticket(call(self.h, jobs, ptr, 1 if device else 0), x, "spx_pipeline_submit_jobs")
 

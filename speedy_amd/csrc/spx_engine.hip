@@ -883,6 +883,7 @@ static int64_t rate_frames(int64_t m, int old_rate, int new_rate) {
 }
 // Workspace of a rate call: the plain call's | SpxRateJob[n] | the walk kernel's counts | the TSM buffers of the jobs with rate != 1
 // (of jobs that have passed spx_check_jobs: spx_internal_out_bound is given no speed that nobody has looked at)
+// rates == nullptr: EVERY job gets its TSM buffer -- what a rate pipeline reserves, whose lanes may all resample in some batch.
 struct RateLayout { size_t off_table, off_tsm_n, off_tsm, total; std::vector<int64_t> tsm_off, tsm_cap; };
 static void rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, RateLayout& RL) {
   size_t o = (spx_batch_workspace_bytes(plan, jobs, n) + 255) & ~(size_t)255;
@@ -892,38 +893,19 @@ static void rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float
   RL.tsm_off.assign(n, 0); RL.tsm_cap.assign(n, 0);
   int64_t v = 0;
   for (int i = 0; i < n; i++) {
-    if (rates[i] == 1.0f) continue;
+    if (rates && rates[i] == 1.0f) continue;
     RL.tsm_off[i] = v;
     RL.tsm_cap[i] = spx_internal_out_bound(plan->dev, jobs[i].n_in, jobs[i].speed, jobs[i].nonlinear != 0.0f);
     v += (RL.tsm_cap[i] * jobs[i].channels + 7) & ~(int64_t)7;   // (every stream's buffer starts on a 16-byte boundary)
   }
   RL.total = o + sizeof(int16_t) * (size_t)v + 128;
 }
-extern "C" {
-int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate) {
-  if (!plan) { fail(-1, "spx_plan_out_capacity_rate: bad arguments"); return -1; }
-  // (the value rules alone: one channel always fits the walk kernel's window)
-  const SpxJobFault f = spx_check_job(spx_job_limits(plan), {0, n_in, 0, 0, 1, speed, nonlinear, 0.0f});
-  if (f != SPX_JOB_OK) return fail(-1, std::string("spx_batch: ") + spx_job_fault_text(f));
-  const int64_t cap = spx_internal_out_bound(plan->dev, n_in, speed, nonlinear != 0.0f);
-  if (rate == 1.0f) return cap;
-  int o = 1, w = 1;
-  if (rate_ratio(plan->dev.rate, rate, &o, &w)) return -1;
-  return rate_frames(cap, o, w) + 1;
-}
-size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams) {
-  if (!rates) return spx_batch_workspace_bytes(plan, jobs, n_streams);
-  if (!plan || !jobs || n_streams < 1) { fail(-1, "spx_batch: bad arguments"); return 0; }
-  bool any = false;
-  for (int i = 0; i < n_streams; i++) { int o, w; if (rate_ratio(plan->dev.rate, rates[i], &o, &w)) return 0; any = any || rates[i] != 1.0f; }
-  if (spx_check_jobs(plan, jobs, n_streams, any)) return 0;
-  RateLayout RL;
-  rate_layout(plan, jobs, rates, n_streams, RL);
-  return RL.total;
-}
-int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
-                       int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
-  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+// What a call with rates hands run_impl (SpxCallOpts::rate): the rates judged, the workspace laid out, the SpxRateJob records and where
+// the walk kernel writes.  ONE builder for the batch call (spx_batch_run_rate) and the pipeline object's rate batches
+// (spx_internal_run_rate).  0 with *any = "a rate other than 1 is there" (false: RC is untouched, the call is spx_batch_run's), or
+// -1 with spx_last_error and nothing enqueued.
+static int rate_call_build(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
+                           const int64_t* n_out, void* ws, size_t ws_bytes, SpxRateCall& RC, bool* any_out) {
   bool any = false;
   std::vector<int> oldR(n, 1), newR(n, 1);
   if (rates)
@@ -931,14 +913,14 @@ int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float*
       if (rate_ratio(plan->dev.rate, rates[i], &oldR[i], &newR[i])) return -1;   // (nothing is launched for a call that is refused)
       any = any || rates[i] != 1.0f;
     }
-  if (!any) return spx_batch_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs);
+  *any_out = any;
+  if (!any) return 0;
   if (!in || !out || !n_out || !ws || (reinterpret_cast<uintptr_t>(out) & 1)) return fail(-1, "spx_batch_run_rate: bad arguments");
   if (spx_check_jobs(plan, jobs, n, true)) return -1;
   RateLayout RL;
   rate_layout(plan, jobs, rates, n, RL);
   if (ws_bytes < RL.total) return fail(-1, "spx_batch_run_rate: workspace too small (spx_batch_workspace_bytes_rate)");
   unsigned char* w = static_cast<unsigned char*>(ws);
-  SpxRateCall RC;
   RC.d_table = reinterpret_cast<SpxRateJob*>(w + RL.off_table);
   RC.d_tsm_n = reinterpret_cast<int64_t*>(w + RL.off_tsm_n);
   RC.tsm_base = reinterpret_cast<const int16_t*>(w + RL.off_tsm);
@@ -965,6 +947,75 @@ int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float*
   static_assert(sizeof(SpxRateJob) % sizeof(int) == 0, "the staging kernel copies 32-bit words");
   RC.table.resize(sizeof(SpxRateJob) / sizeof(int) * (size_t)n);
   memcpy(RC.table.data(), tab.data(), sizeof(SpxRateJob) * (size_t)n);
+  return 0;
+}
+// ---- the pipeline object's side of the rate call (spx_pipeline.hip) ----
+// One rate as spx_batch_run_rate judges it: 0, or -1 with the message.
+int spx_internal_rate_check(spx_plan_t plan, float rate) {
+  int o = 1, w = 1;
+  return plan ? rate_ratio(plan->dev.rate, rate, &o, &w) : fail(-1, "spx_batch: bad arguments");
+}
+// The workspace of a rate call in which EVERY job resamples: no table of rates over these jobs needs more.  0 with spx_last_error
+// for a table the rate call refuses.
+size_t spx_internal_rate_workspace_all(spx_plan_t plan, const spx_stream_job* jobs, int n) {
+  if (spx_check_jobs(plan, jobs, n, true)) return 0;
+  RateLayout RL;
+  rate_layout(plan, jobs, nullptr, n, RL);
+  return RL.total;
+}
+// A batch with at least one rate other than 1 for the pipeline object: spx_batch_run_rate -- the plain call, kernels in sequence on
+// hs -- behind in_ready (a hipEvent_t or null), with done_event (or null) recorded behind the rate kernel.
+// ORDER against the overlapped calls the same pipeline makes on the same plan.  Buffers: every call has its own workspace, out and
+// n_out (the pipeline's slot), handed over again only after the host has waited for the slot's event; the job tables travel through
+// the plan's two pinned staging slots, each reused only after a host wait for the kernel that last read it (stage_tables).  Plan
+// state: ring_note / ring_record are made under the plan's mutex, in call order; this call leaves its end in the ring on hs itself,
+// so a later overlapped call that must wait for it (same workspace, the ring's older half) waits for the rate kernel, and it clears
+// ahead_started, so the next overlapped call's staging kernel runs no gate on a counter this call's walk kernel never raises.
+// Streams: the call uses hs alone (the side stream only for a call of more than two streams per CU, whose chunks it orders with
+// its own events), and on a pipeline whose calls are not detached hs already waits for every earlier walk kernel (ring_record);
+// on a detached pipeline it runs beside them, on other buffers.
+int spx_internal_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
+                          int64_t* n_out, void* ws, size_t ws_bytes, void* hs, void* in_ready, void* done_event) {
+  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+  SpxRateCall RC;
+  bool any = false;
+  if (rate_call_build(plan, jobs, rates, n, in, out, n_out, ws, ws_bytes, RC, &any)) return -1;
+  if (!any) return fail(-1, "spx_pipeline: internal: a batch of ones is not a rate call");
+  SpxCallOpts o;
+  o.rate = &RC;
+  o.in_ready = in_ready;
+  o.done_event = done_event;
+  return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, nullptr, hs, true, true, o);
+}
+extern "C" {
+int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate) {
+  if (!plan) { fail(-1, "spx_plan_out_capacity_rate: bad arguments"); return -1; }
+  // (the value rules alone: one channel always fits the walk kernel's window)
+  const SpxJobFault f = spx_check_job(spx_job_limits(plan), {0, n_in, 0, 0, 1, speed, nonlinear, 0.0f});
+  if (f != SPX_JOB_OK) return fail(-1, std::string("spx_batch: ") + spx_job_fault_text(f));
+  const int64_t cap = spx_internal_out_bound(plan->dev, n_in, speed, nonlinear != 0.0f);
+  if (rate == 1.0f) return cap;
+  int o = 1, w = 1;
+  if (rate_ratio(plan->dev.rate, rate, &o, &w)) return -1;
+  return rate_frames(cap, o, w) + 1;
+}
+size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams) {
+  if (!rates) return spx_batch_workspace_bytes(plan, jobs, n_streams);
+  if (!plan || !jobs || n_streams < 1) { fail(-1, "spx_batch: bad arguments"); return 0; }
+  bool any = false;
+  for (int i = 0; i < n_streams; i++) { int o, w; if (rate_ratio(plan->dev.rate, rates[i], &o, &w)) return 0; any = any || rates[i] != 1.0f; }
+  if (spx_check_jobs(plan, jobs, n_streams, any)) return 0;
+  RateLayout RL;
+  rate_layout(plan, jobs, rates, n_streams, RL);
+  return RL.total;
+}
+int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
+                       int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
+  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+  SpxRateCall RC;
+  bool any = false;
+  if (rate_call_build(plan, jobs, rates, n, in, out, n_out, ws, ws_bytes, RC, &any)) return -1;
+  if (!any) return spx_batch_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs);
   SpxCallOpts o;
   o.rate = &RC;
   return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, o);

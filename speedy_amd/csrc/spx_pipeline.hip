@@ -43,6 +43,16 @@
 // the jobs' values, and `in` says when it has been read.  No stream is added to the five the library holds.
 // Measured (profiles/pipeline_float.txt, 256 x 10 s): the conversions take 55 and 24 us, the float gather 0.99 ms for 53.5 MB (the int16
 // one 0.49 for half the bytes: the link's rate both); host to host 3.36 ms per batch over a 2.88 ms copy of the 164 MB input.
+//
+// PLAYBACK RATES (spx_pipeline_create_rate): a one-plan pipeline whose capacities count FINAL frames (spx_plan_out_capacity_rate at the
+// rate each lane is sized for) and whose workspace holds the rate call's TSM staging of EVERY lane.  A ticket carries a rate per lane
+// beside its job table.  All ones: nothing above changes.  One rate other than 1: the engine runs the batch as spx_batch_run_rate does
+// (spx_engine.hip spx_internal_run_rate: the same builder, the plain call) on the RUN stream behind `in`; the tails follow as they are.
+//   copy stream   as above (float: with the conversion)  ->  record(in)
+//   run stream    wait(in)  ->  staging, analysis, tension, general walk kernel (no flush truncation, into the slot's workspace),
+//                 spx_rate_batch_kernel into the slot's d_out  ->  offsets + gather (or the float conversion)  ->  record(done)
+// Never detached; no stream is added.  DESIGN.md "The rate pipeline" says where the order against neighbouring overlapped calls
+// comes from.
 #include <string.h>
 
 #include <string>
@@ -59,6 +69,11 @@ int spx_internal_run_mixed(const spx_plan_t* plans, int n_plans, const spx_strea
                            int16_t* out, int64_t* n_out, void* ws, size_t ws_bytes, void* hs, bool ahead, void* in_ready,
                            void* done_event, bool detached);
 void spx_internal_set_error(const char* msg);
+// spx_engine.hip: the rate call's side of a rate pipeline (spx_pipeline_create_rate)
+int spx_internal_rate_check(spx_plan_t plan, float rate);
+size_t spx_internal_rate_workspace_all(spx_plan_t plan, const spx_stream_job* jobs, int n);
+int spx_internal_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
+                          int64_t* n_out, void* ws, size_t ws_bytes, void* hs, void* in_ready, void* done_event);
 // spx_convert.hip: the float batch call's conversion table and its two kernels, launched for a buffer set of the pipeline's
 size_t spx_conv_table_bytes(int n);
 int spx_conv_table_fill(void* pinned, const spx_stream_job* jobs, int n, int* max_in, int* max_out);
@@ -186,6 +201,8 @@ struct spx_pipeline {
   std::vector<spx_plan_t> plans;
   std::vector<int> plan_index;
   bool mixed = false;
+  bool rate_kind = false;             // made by spx_pipeline_create_rate: capacities in final frames, every lane's TSM staging in the workspace
+  std::vector<float> rates;           // ... and the rate every lane was sized for: the rates of spx_pipeline_submit
   int n = 0, depth = 0;
   unsigned flags = 0;
   int device = 0;
@@ -250,10 +267,17 @@ static int lane_check(const spx_pipeline* p, int lane, const spx_stream_job& j) 
   return f == SPX_JOB_OK ? 0 : lane_fail(lane, spx_job_fault_text(f));
 }
 
+// A lane's rate by spx_batch_run_rate's rule, in its words, with the lane and the rate in front
+static int lane_rate_check(const spx_pipeline* p, int lane, float rate) {
+  if (spx_internal_rate_check(p->plans[0], rate) == 0) return 0;
+  return lane_fail(lane, "rate " + std::to_string(rate) + ": " + spx_last_error());
+}
+
 static int pipeline_build(spx_pipeline* p) {
   const int n = p->n;
   PCHK(hipGetDevice(&p->device));
-  // the pipeline's own output layout: capacity per stream as spx_plan_out_capacity_for, regions at 64-byte boundaries
+  // the pipeline's own output layout: capacity per stream as spx_plan_out_capacity_for (a rate pipeline: _rate, FINAL frames at the
+  // rate the lane is sized for), regions at 64-byte boundaries
   int64_t oo = 0;
   size_t in_values = 0;
   std::vector<int64_t> tab((size_t)2 * n);
@@ -264,7 +288,10 @@ static int pipeline_build(spx_pipeline* p) {
     j.out_off = j.out_cap = 0;   // (the caller's are not read: the pipeline lays its own output out below)
     if (lane_check(p, i, j)) return -1;
     spx_plan_t pl = p->plans[p->mixed ? p->plan_index[i] : 0];
-    j.out_cap = spx_plan_out_capacity_for(pl, j.n_in, j.speed, j.nonlinear);
+    if (p->rate_kind && lane_rate_check(p, i, p->rates[i])) return -1;
+    j.out_cap = p->rate_kind ? spx_plan_out_capacity_rate(pl, j.n_in, j.speed, j.nonlinear, p->rates[i])
+                             : spx_plan_out_capacity_for(pl, j.n_in, j.speed, j.nonlinear);
+    if (j.out_cap < 0) return lane_fail(i, spx_last_error());
     j.out_off = oo;
     p->static_offsets[i] = oo;
     tab[i] = oo; tab[(size_t)n + i] = j.out_cap; chans[i] = j.channels;
@@ -275,8 +302,11 @@ static int pipeline_build(spx_pipeline* p) {
   p->static_offsets[n] = oo;
   p->in_values = in_values;
   p->out_values = (size_t)oo;
+  // (a rate pipeline: the rate call's workspace with the TSM staging of EVERY lane, also of those sized for rate 1 -- any lane may
+  // resample in some batch; it begins with the plain call's workspace, which is what a batch of ones runs in)
   p->ws_bytes = p->mixed ? spx_batch_workspace_bytes_mixed(p->plans.data(), (int)p->plans.size(), p->jobs.data(), p->plan_index.data(), n)
-                         : spx_batch_workspace_bytes(p->plans[0], p->jobs.data(), n);
+                         : (p->rate_kind ? spx_internal_rate_workspace_all(p->plans[0], p->jobs.data(), n)
+                                         : spx_batch_workspace_bytes(p->plans[0], p->jobs.data(), n));
   if (!p->ws_bytes) return -1;
   PCHK(hipStreamCreateWithFlags(&p->s_run, hipStreamNonBlocking));
   PCHK(hipStreamCreateWithFlags(&p->s_h2d, hipStreamNonBlocking));
@@ -348,6 +378,25 @@ spx_pipeline_t spx_pipeline_create(spx_plan_t plan, const spx_stream_job* jobs, 
   if (!plan) { pfail(-1, "spx_pipeline_create: no plan"); return nullptr; }
   return spx_pipeline_create_mixed(&plan, 1, jobs, nullptr, n_streams, depth, flags);
 }
+spx_pipeline_t spx_pipeline_create_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, int depth,
+                                        unsigned flags) {
+  if (!plan) { pfail(-1, "spx_pipeline_create_rate: no plan"); return nullptr; }
+  if (!jobs || n_streams < 1 || depth < 0 || depth == 1 || depth > SPX_PIPE_MAX_DEPTH) {
+    pfail(-1, "spx_pipeline_create_rate: bad arguments (depth 0 or 2 .. 8)");
+    return nullptr;
+  }
+  spx_pipeline* p = new spx_pipeline();
+  p->plans.assign(1, plan);
+  p->rate_kind = true;
+  if (rates) p->rates.assign(rates, rates + n_streams);
+  else p->rates.assign((size_t)n_streams, 1.0f);
+  p->n = n_streams;
+  p->depth = depth ? depth : 4;
+  p->flags = flags;
+  p->jobs.assign(jobs, jobs + n_streams);
+  if (pipeline_build(p)) { pipeline_free(p); return nullptr; }
+  return p;
+}
 void spx_pipeline_destroy(spx_pipeline_t p) { pipeline_free(p); }
 int spx_pipeline_depth(spx_pipeline_t p) { return p ? p->depth : 0; }
 size_t spx_pipeline_input_values(spx_pipeline_t p) { return p ? p->in_values : 0; }
@@ -404,8 +453,14 @@ static int pipeline_float_input(spx_pipeline_t p, SpxPipeSlot& S, size_t extent,
 
 // One batch with the table `jobs` (the pipeline's own layout in it) and `extent` values of input: int16, or float on a pipeline
 // created with SPX_PIPELINE_FLOAT.
-static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, size_t extent, const void* in_any, int in_is_device) {
+// rates (a rate pipeline's batch; null = every rate 1): a batch of ones takes the overlapped order every pipeline batch takes; with one
+// rate other than 1 the engine runs the batch as spx_batch_run_rate does -- general walk kernel into the TSM staging of the slot's
+// workspace, rate kernel into the slot's d_out, kernels in sequence on the run stream behind ev_in -- and the tails follow unchanged.
+static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates, size_t extent, const void* in_any,
+                               int in_is_device) {
   const bool flt = (p->flags & SPX_PIPELINE_FLOAT) != 0;
+  bool resample = false;
+  for (int i = 0; rates && i < p->n; i++) resample = resample || rates[i] != 1.0f;
   const int16_t* in = flt ? nullptr : static_cast<const int16_t*>(in_any);
   const int64_t ticket = p->next_ticket;
   SpxPipeSlot& S = p->slots[(size_t)(ticket % p->depth)];
@@ -446,7 +501,11 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, siz
   // cannot be detached from it and takes the order the host-output pipeline takes)
   bool event_recorded = false;
   const bool detach = !host_out && !flt;
-  if (p->mixed) {
+  if (resample) {
+    // (never detached: the rate kernel ends the call on the run stream, where the slot's event is recorded below.  The rates are read
+    // before the call returns: they reach the device inside the SpxRateJob records, through the engine's staging kernel)
+    rc = spx_internal_run_rate(p->plans[0], S.jobs.data(), rates, p->n, dev_in, S.d_out, S.d_nout, S.ws, p->ws_bytes, p->s_run, in_ready, nullptr);
+  } else if (p->mixed) {
     // (round 6: detached like a one-plan batch -- the groups' walk kernels on the library's walk streams, two calls' worth in flight)
     rc = spx_internal_run_mixed(p->plans.data(), (int)p->plans.size(), S.jobs.data(), p->plan_index.data(), p->n, dev_in, S.d_out, S.d_nout,
                                 S.ws, p->ws_bytes, p->s_run, true, in_ready, detach ? S.ev_done : nullptr, detach);
@@ -491,7 +550,11 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, siz
 // The limits are the pipeline's own: the lane's channel count, the input buffer, the lane's output capacity, the workspace.
 // A job's VALUES are judged by the engine's rules (lane_check: spx_jobs.h, the rules every batch call applies at its top), asked
 // here per lane so that the message names the lane and comes before the wait for the buffer set and the copy in.
-static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, std::vector<spx_stream_job>& table, size_t* extent) {
+// rates (a rate pipeline only; null = every rate 1): each one spx_batch_run_rate takes, the capacity rule in FINAL frames
+// (spx_plan_out_capacity_rate at THIS batch's rate against the lane's capacity at creation -- the inequality itself, not "rate >=
+// creation rate": rate_ratio halves both sample rates to 14 bits, so the capacity is not promised monotone in the rate), and the
+// workspace rule against spx_batch_workspace_bytes_rate of the table with these rates.
+static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates, std::vector<spx_stream_job>& table, size_t* extent) {
   const int n = p->n;
   table.assign(jobs, jobs + n);
   size_t ext = 0;
@@ -503,11 +566,21 @@ static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, std::vec
     j.out_off = c.out_off;
     j.out_cap = c.out_cap;
     if (lane_check(p, i, j)) return -1;
+    if (rates && lane_rate_check(p, i, rates[i])) return -1;
     if ((uint64_t)j.in_off > p->in_values || (uint64_t)j.n_in * (uint64_t)j.channels > p->in_values - (uint64_t)j.in_off)
       return lane_fail(i, "in_off " + std::to_string(j.in_off) + " + n_in " + std::to_string(j.n_in) + " x " + std::to_string(j.channels) +
                               " channels ends behind the pipeline's input of " + std::to_string(p->in_values) + " values (spx_pipeline_input_values)");
     const size_t end = (size_t)j.in_off + (size_t)j.n_in * (size_t)j.channels;
     if (end > ext) ext = end;
+    if (rates && rates[i] != 1.0f) {
+      const int64_t fin = spx_plan_out_capacity_rate(p->plans[0], j.n_in, j.speed, j.nonlinear, rates[i]);
+      if (fin < 0) return lane_fail(i, spx_last_error());
+      if (fin > c.out_cap)
+        return lane_fail(i, "n_in " + std::to_string(j.n_in) + " at speed " + std::to_string(j.speed) + (j.nonlinear != 0.0f ? " nonlinear" : " linear") +
+                                " and rate " + std::to_string(rates[i]) + " needs an output capacity of " + std::to_string(fin) +
+                                " final frames (spx_plan_out_capacity_rate), the lane was created with " + std::to_string(c.out_cap));
+      continue;
+    }
     const int64_t need = spx_plan_out_capacity_for(p->plans[p->mixed ? p->plan_index[i] : 0], j.n_in, j.speed, j.nonlinear);
     if (need > c.out_cap)
       return lane_fail(i, "n_in " + std::to_string(j.n_in) + " at speed " + std::to_string(j.speed) + (j.nonlinear != 0.0f ? " nonlinear" : " linear") +
@@ -515,8 +588,22 @@ static int pipeline_check(spx_pipeline_t p, const spx_stream_job* jobs, std::vec
                               std::to_string(c.out_cap));
   }
   const size_t ws = p->mixed ? spx_batch_workspace_bytes_mixed(p->plans.data(), (int)p->plans.size(), table.data(), p->plan_index.data(), n)
-                             : spx_batch_workspace_bytes(p->plans[0], table.data(), n);
+                             : (rates ? spx_batch_workspace_bytes_rate(p->plans[0], table.data(), rates, n)
+                                      : spx_batch_workspace_bytes(p->plans[0], table.data(), n));
   if (!ws) return -1;   // (the engine could not lay the table out: its own message stands)
+  if (ws > p->ws_bytes && rates) {
+    // a rate batch's workspace also holds the speed stage's output of the lanes that resample: name the first lane that has more
+    // analysis frames, or more speed-stage frames to stage, than it was created with
+    int lane = 0;
+    for (int i = 0; i < n; i++) {
+      const spx_stream_job &j = table[i], &c = p->jobs[i];
+      const int64_t now = j.nonlinear != 0.0f ? spx_plan_frames(p->plans[0], j.n_in) : 0;
+      const int64_t then = c.nonlinear != 0.0f ? spx_plan_frames(p->plans[0], c.n_in) : 0;
+      if (now > then || spx_plan_out_capacity_for(p->plans[0], j.n_in, j.speed, j.nonlinear) > spx_plan_out_capacity_for(p->plans[0], c.n_in, c.speed, c.nonlinear)) { lane = i; break; }
+    }
+    return lane_fail(lane, "more analysis frames or more speed-stage frames to resample than the lane was created with: the batch needs a workspace of " +
+                               std::to_string(ws) + " bytes (spx_batch_workspace_bytes_rate), the pipeline's holds " + std::to_string(p->ws_bytes));
+  }
   if (ws > p->ws_bytes) {
     // the workspace grows with the analysis frames of the nonlinear lanes: name the first lane that has more of them than it was created with
     int lane = 0;
@@ -543,7 +630,7 @@ extern "C" {
 int64_t spx_pipeline_submit(spx_pipeline_t p, const int16_t* in, int in_is_device) {
   if (!p || !in) return pfail(-1, "spx_pipeline_submit: bad arguments");
   if (wrong_kind(p, false, "spx_pipeline_submit") || pipeline_current(p, "spx_pipeline_submit")) return -1;
-  return pipeline_submit(p, p->jobs.data(), p->in_values, in, in_is_device);
+  return pipeline_submit(p, p->jobs.data(), p->rate_kind ? p->rates.data() : nullptr, p->in_values, in, in_is_device);
 }
 static int float_aligned(const float* in, const char* who) {
   if (reinterpret_cast<uintptr_t>(in) & 3) return pfail(-1, std::string(who) + ": in must be 4-byte aligned");
@@ -553,21 +640,21 @@ int64_t spx_pipeline_submit_float(spx_pipeline_t p, const float* in, int in_is_d
   if (!p || !in) return pfail(-1, "spx_pipeline_submit_float: bad arguments");
   if (wrong_kind(p, true, "spx_pipeline_submit_float") || float_aligned(in, "spx_pipeline_submit_float") ||
       pipeline_current(p, "spx_pipeline_submit_float")) return -1;
-  return pipeline_submit(p, p->jobs.data(), p->in_values, in, in_is_device);
+  return pipeline_submit(p, p->jobs.data(), p->rate_kind ? p->rates.data() : nullptr, p->in_values, in, in_is_device);
 }
 int spx_pipeline_jobs_fit(spx_pipeline_t p, const spx_stream_job* jobs) {
   if (!p || !jobs) return pfail(-1, "spx_pipeline_jobs_fit: bad arguments");
   std::vector<spx_stream_job> table;
   size_t extent = 0;
-  return pipeline_check(p, jobs, table, &extent);
+  return pipeline_check(p, jobs, nullptr, table, &extent);
 }
 int64_t spx_pipeline_submit_jobs(spx_pipeline_t p, const spx_stream_job* jobs, const int16_t* in, int in_is_device) {
   if (!p || !jobs || !in) return pfail(-1, "spx_pipeline_submit_jobs: bad arguments");
   if (wrong_kind(p, false, "spx_pipeline_submit_jobs") || pipeline_current(p, "spx_pipeline_submit_jobs")) return -1;
   std::vector<spx_stream_job> table;
   size_t extent = 0;
-  if (pipeline_check(p, jobs, table, &extent)) return -1;   // (before anything is waited for, copied or enqueued: no ticket is used up)
-  return pipeline_submit(p, table.data(), extent, in, in_is_device);
+  if (pipeline_check(p, jobs, nullptr, table, &extent)) return -1;   // (before anything is waited for, copied or enqueued: no ticket is used up)
+  return pipeline_submit(p, table.data(), nullptr, extent, in, in_is_device);
 }
 int64_t spx_pipeline_submit_jobs_float(spx_pipeline_t p, const spx_stream_job* jobs, const float* in, int in_is_device) {
   if (!p || !jobs || !in) return pfail(-1, "spx_pipeline_submit_jobs_float: bad arguments");
@@ -575,8 +662,39 @@ int64_t spx_pipeline_submit_jobs_float(spx_pipeline_t p, const spx_stream_job* j
       pipeline_current(p, "spx_pipeline_submit_jobs_float")) return -1;
   std::vector<spx_stream_job> table;
   size_t extent = 0;
-  if (pipeline_check(p, jobs, table, &extent)) return -1;
-  return pipeline_submit(p, table.data(), extent, in, in_is_device);
+  if (pipeline_check(p, jobs, nullptr, table, &extent)) return -1;
+  return pipeline_submit(p, table.data(), nullptr, extent, in, in_is_device);
+}
+
+// ---- the _rate calls: a rate pipeline's batch with its own rate per lane (rates == NULL: every rate 1) ----
+static int rate_pipeline_only(const spx_pipeline* p, const char* who) {
+  if (p->rate_kind) return 0;
+  return pfail(-1, std::string(who) + ": the pipeline takes no playback rates: create it with spx_pipeline_create_rate");
+}
+int spx_pipeline_jobs_fit_rate(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates) {
+  if (!p || !jobs) return pfail(-1, "spx_pipeline_jobs_fit_rate: bad arguments");
+  if (rate_pipeline_only(p, "spx_pipeline_jobs_fit_rate")) return -1;
+  std::vector<spx_stream_job> table;
+  size_t extent = 0;
+  return pipeline_check(p, jobs, rates, table, &extent);
+}
+int64_t spx_pipeline_submit_jobs_rate(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates, const int16_t* in, int in_is_device) {
+  if (!p || !jobs || !in) return pfail(-1, "spx_pipeline_submit_jobs_rate: bad arguments");
+  if (rate_pipeline_only(p, "spx_pipeline_submit_jobs_rate") || wrong_kind(p, false, "spx_pipeline_submit_jobs_rate") ||
+      pipeline_current(p, "spx_pipeline_submit_jobs_rate")) return -1;
+  std::vector<spx_stream_job> table;
+  size_t extent = 0;
+  if (pipeline_check(p, jobs, rates, table, &extent)) return -1;   // (before anything is waited for, copied or enqueued: no ticket is used up)
+  return pipeline_submit(p, table.data(), rates, extent, in, in_is_device);
+}
+int64_t spx_pipeline_submit_jobs_rate_float(spx_pipeline_t p, const spx_stream_job* jobs, const float* rates, const float* in, int in_is_device) {
+  if (!p || !jobs || !in) return pfail(-1, "spx_pipeline_submit_jobs_rate_float: bad arguments");
+  if (rate_pipeline_only(p, "spx_pipeline_submit_jobs_rate_float") || wrong_kind(p, true, "spx_pipeline_submit_jobs_rate_float") ||
+      float_aligned(in, "spx_pipeline_submit_jobs_rate_float") || pipeline_current(p, "spx_pipeline_submit_jobs_rate_float")) return -1;
+  std::vector<spx_stream_job> table;
+  size_t extent = 0;
+  if (pipeline_check(p, jobs, rates, table, &extent)) return -1;
+  return pipeline_submit(p, table.data(), rates, extent, in, in_is_device);
 }
 
 static SpxPipeSlot* slot_of(spx_pipeline_t p, int64_t ticket) {
