@@ -91,7 +91,7 @@ size_t spx_batch_workspace_bytes(spx_plan_t plan, const spx_stream_job* jobs, in
  * [0, 1], the feedback strength is finite, n_in < 2^30 and -- a nonlinear job -- the plan's analysis tile fits one CU's LDS;
  * a batch if the walk kernel's window of its largest channel count fits a CU's LDS.  The whole table is judged by these rules
  * before anything is enqueued: -1 with the first broken rule in spx_last_error, nothing launched, the plan as it was.  That
- * holds for every batch call below -- _ahead / _overlapped (also where the call is cut into sub-batches), _mixed*, _rate, _float:
+ * holds for every batch call below -- _ahead / _overlapped (also where the call is cut into sub-batches), _mixed*, _rate, _float, _map:
  * the bad job may be the last of the last group -- and the rate / float workspace and capacity queries answer 0 / -1 for such
  * a table; spx_pipeline_create* and spx_pipeline_submit_jobs / _jobs_fit apply the same rules per lane and name the lane. */
 int spx_batch_run(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int16_t* in,
@@ -118,6 +118,46 @@ size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* job
 /* spx_plan_out_capacity_for behind the rate stage: safe capacity in FINAL frames; -1 (spx_last_error) for a rate, speed,
  * nonlinear factor or n_in that is refused. */
 int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate);
+
+/* ---- TIME MAP: which output frame each 10 ms of input lands on ----
+ * A nonlinear speed-up changes its speed every 10 ms; spx_batch_run_map is spx_batch_run that also writes down where the input
+ * went, for callers whose audio carries timestamps (captions, word or phone labels, a video track).  With B = spx_plan_frame_step
+ * and R = n_in / B (integer division) a job's rows M are
+ *   nonlinear != 0   R + 1 rows: M[k], k < R, = the output frames the time-scale stage has produced when ring buffer k -- input
+ *                    frames [kB, (k+1)B) -- is about to be handed to it; M[R] = the job's final count, the value of n_out
+ *   nonlinear == 0   one row, M[0] = n_out.
+ * spx_plan_map_rows returns that row count (-1 for a null plan or a negative n_in).  M[0] = 0 where R >= 1, and the rows never
+ * decrease; consecutive rows are often equal, because the time-scale stage works in whole pitch periods.  It also holds back up to
+ * about spx_plan_max_required input frames before it emits anything for them: the map is LATE by at most that -- a few tens of
+ * milliseconds -- and never early.  (The integral of 1 / speed over the speed tap is no substitute: it drifts from these rows.)
+ *   map  DEVICE int64; stream i's rows start at the sum of spx_plan_map_rows of the streams in front of it, in job order.
+ * out, n_out and the taps are byte for byte spx_batch_run's for the same table; the workspace is spx_batch_workspace_bytes.  The
+ * call refuses what spx_batch_run refuses, with the same messages, and a NULL map -- -1, spx_last_error, nothing enqueued.  The rows
+ * of a job whose n_out comes back negative are unspecified.
+ * COST: the whole batch runs on the GENERAL walk kernel (the speed-up kernels write no map yet), kernels in sequence on hip_stream,
+ * as spx_batch_run_rate does: profiles/time_map.txt.  The plain call only.  OUT OF SCOPE: a map on the _rate, _float, _ahead,
+ * _overlapped and _mixed* calls, on the pipeline object and on the streaming API (include/sonic2.h).
+ *
+ * spx_map_lookup converts positions on the device, asynchronous on hip_stream, in exact integer arithmetic (int64, floor division).
+ *   jobs     HOST   the table the map was made with (n_in and nonlinear are read)
+ *   map      DEVICE the rows spx_batch_run_map wrote
+ *   q_off    DEVICE int64[n_streams + 1]: stream i's queries are q[q_off[i] .. q_off[i + 1]) (an empty range is fine)
+ *   q, r     DEVICE int64: positions in, positions out, same indices
+ *   inverse  0: input frame -> output frame; otherwise output frame -> input frame
+ * Nodes: X = [0, B, .., (R-1)B, n_in], Y = M for R >= 1;  X = [0, n_in], Y = [0, M[0]] for R = 0 (a linear job, or one shorter
+ * than a ring buffer).  L = the number of nodes.
+ *   forward  t clamped to [0, n_in]; n_in = 0 gives 0; else j = min(t / B, L - 2) and
+ *            Y[j] + (t - X[j]) * (Y[j+1] - Y[j]) / (X[j+1] - X[j])
+ *   inverse  u clamped to [0, Y[L-1]]; u >= Y[L-1] gives n_in; else j = the largest index with Y[j] <= u (a flat run resolves
+ *            to its last node, so Y[j+1] > u) and  X[j] + (u - Y[j]) * (X[j+1] - X[j]) / (Y[j+1] - Y[j])
+ * Both are non-decreasing, and forward(inverse(u)) <= u.  Returns 0, or -1 (spx_last_error) for a null pointer or a table
+ * spx_batch_run refuses. */
+int64_t spx_plan_map_rows(spx_plan_t plan, int64_t n_in, float nonlinear);
+int spx_batch_run_map(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int16_t* in,
+                      int16_t* out, int64_t* n_out, int64_t* map, void* workspace, size_t workspace_bytes,
+                      const spx_taps* taps, void* hip_stream);
+int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int64_t* map, const int64_t* q_off,
+                   const int64_t* q, int64_t* r, int inverse, void* hip_stream);
 
 /* spx_batch_run_rate on FLOAT samples in device memory (sonicWriteFloatToStream / sonicReadFloatFromStream, sonic2.h:64-68).
  *   in   DEVICE  float input samples in (-1, 1), 4-byte aligned; read once, exactly the jobs' values: no padding behind the end

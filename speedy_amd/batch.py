@@ -46,13 +46,22 @@ class Plan:
 class Batch:
     """A prepared batch: inputs packed into one HBM buffer, outputs and workspace allocated once.
     rate: a playback rate (sonicSetRate) for every stream or one per stream -- run() is then spx_batch_run_rate and the
-    outputs are the final frames behind the rate stage; None: spx_batch_run, call for call as before."""
+    outputs are the final frames behind the rate stage; None: spx_batch_run, call for call as before.
+    time_map: run() is spx_batch_run_map -- the same outputs, counts and taps, and a time map beside them: time_map(i) returns
+    stream i's rows (the output frames produced when each 10 ms ring buffer of input is handed to the time-scale stage, then the
+    final count), lookup(i, positions) converts input frames to output frames (inverse=True: the other way) on the GPU.  The plain
+    call only: no rate, no run_ahead."""
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
-                 spectrogram_taps=False, rate=None):
+                 spectrogram_taps=False, rate=None, time_map=False):
+        if time_map and not torch.cuda.is_available():
+            raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
+        if time_map and rate is not None:
+            raise ValueError("a time map comes with the plain call only (spx_batch_run_map has no rate form)")
         self.plan = plan
         n = len(lengths)
         self.n = n
+        self.with_map = bool(time_map)
         self.rates = None
         if rate is not None:
             if not torch.cuda.is_available():
@@ -96,6 +105,12 @@ class Batch:
             if wsb == 0:
                 raise RuntimeError("spx_batch_workspace_bytes_rate: " + plan.L.spx_last_error().decode())
         self.d_ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
+        if self.with_map:
+            # stream i's rows: d_map[map_offs[i] : map_offs[i + 1]] (spx_plan_map_rows per job, in job order)
+            self.map_offs = [0]
+            for i in range(n):
+                self.map_offs.append(self.map_offs[-1] + plan.L.spx_plan_map_rows(plan.h, int(self.lengths[i]), float(nlv[i])))
+            self.d_map = torch.zeros(self.map_offs[-1], dtype=torch.int64, device=dev)
         self.taps = None
         if taps:
             T1 = max(1, fo)
@@ -132,6 +147,13 @@ class Batch:
             if rc != 0:
                 raise RuntimeError("spx_batch_run_rate: " + self.plan.L.spx_last_error().decode())
             return
+        if self.with_map:
+            rc = self.plan.L.spx_batch_run_map(self.plan.h, self.jobs, self.n, self.d_in.data_ptr(), self.d_out.data_ptr(),
+                                               self.d_nout.data_ptr(), self.d_map.data_ptr(), self.d_ws.data_ptr(), self.d_ws.numel(),
+                                               C.byref(self.taps) if self.taps is not None else None, hs)
+            if rc != 0:
+                raise RuntimeError("spx_batch_run_map: " + self.plan.L.spx_last_error().decode())
+            return
         rc = self.plan.L.spx_batch_run(self.plan.h, self.jobs, self.n, self.d_in.data_ptr(), self.d_out.data_ptr(),
                                        self.d_nout.data_ptr(), self.d_ws.data_ptr(), self.d_ws.numel(),
                                        C.byref(self.taps) if self.taps is not None else None, hs)
@@ -145,6 +167,8 @@ class Batch:
         too; nothing enqueued between two calls may touch the later call's buffers (include/speedy_hip.h)."""
         if self.rates is not None:
             raise RuntimeError("a batch with rates runs through the plain call only (spx_batch_run_rate)")
+        if self.with_map:
+            raise RuntimeError("a batch with a time map runs through the plain call only (spx_batch_run_map)")
         hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
         if overlap:
             assert in_ready is None
@@ -201,6 +225,43 @@ class Batch:
         if rc != 0:
             raise RuntimeError("spx_batch_pack_outputs: " + self.plan.L.spx_last_error().decode())
         return self.d_packed, self.d_offsets
+
+    def time_map(self, i):
+        """Stream i's time-map rows of the last run (host numpy int64): for a nonlinear stream row k < n_in // B is the number of
+        output frames produced when input frames [k B, (k + 1) B) are handed to the time-scale stage, the last row is the final
+        count; a linear stream has the final count alone."""
+        if not self.with_map:
+            raise RuntimeError("the batch was made without time_map=True")
+        torch.cuda.synchronize(self.device)
+        return self.d_map[self.map_offs[i]:self.map_offs[i + 1]].cpu().numpy().copy()
+
+    def lookup_all(self, positions, inverse=False, stream=None):
+        """spx_map_lookup over the whole batch: positions[i] = stream i's queries (any int sequence, may be empty).  Input frames to
+        output frames, inverse=True: output frames to input frames; exact integer interpolation between the map's nodes
+        (include/speedy_hip.h).  Returns a list of int64 numpy arrays."""
+        if not self.with_map:
+            raise RuntimeError("the batch was made without time_map=True")
+        assert len(positions) == self.n
+        qs = [np.ascontiguousarray(p, np.int64).ravel() for p in positions]
+        offs = np.zeros(self.n + 1, np.int64)
+        offs[1:] = np.cumsum([q.size for q in qs])
+        total = int(offs[-1])
+        d_off = torch.from_numpy(offs).to(self.device)
+        d_q = torch.from_numpy(np.concatenate(qs) if total else np.zeros(1, np.int64)).to(self.device)
+        d_r = torch.zeros_like(d_q)
+        hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        rc = self.plan.L.spx_map_lookup(self.plan.h, self.jobs, self.n, self.d_map.data_ptr(), d_off.data_ptr(), d_q.data_ptr(),
+                                        d_r.data_ptr(), 1 if inverse else 0, hs)
+        if rc != 0:
+            raise RuntimeError("spx_map_lookup: " + self.plan.L.spx_last_error().decode())
+        torch.cuda.synchronize(self.device)
+        res = d_r.cpu().numpy()
+        return [res[int(offs[i]):int(offs[i + 1])].copy() for i in range(self.n)]
+
+    def lookup(self, i, positions, inverse=False):
+        """Stream i's positions through the time map: input frames to output frames (inverse=True: the other way)."""
+        empty = np.zeros(0, np.int64)
+        return self.lookup_all([positions if k == i else empty for k in range(self.n)], inverse)[i]
 
     def tap_arrays(self, i):
         """tension/speed/features rows of stream i (host numpy)."""

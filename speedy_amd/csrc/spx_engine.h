@@ -152,6 +152,8 @@ static inline int64_t frames_for(const SpxPlanDev& d, int64_t n_in) {
   if (n_in < d.W + 1) return 0;
   return (n_in - d.W - 1) / d.B + 1;
 }
+// rows of a job's time map (spx_plan_map_rows): one per complete ring buffer and the final count; a linear job has the count alone
+static inline int64_t spx_map_rows(const SpxPlanDev& d, int64_t n_in, bool nonlinear) { return nonlinear ? n_in / d.B + 1 : 1; }
 spx_plan* shared_plan_full(int sample_rate, int match_matlab);   // spx_plan.hip: one plan per (device, rate, hysteresis mode), cached
 
 // ---- spx_engine.hip ----
@@ -198,6 +200,9 @@ struct SpxRateCall {
 struct SpxCallOpts {
   const SpxForce* force = nullptr;
   const SpxRateCall* rate = nullptr;   // spx_batch_run_rate with at least one rate != 1
+  // spx_batch_run_map: DEVICE, the call's time map (spx_map_rows per job, in job order).  Handled like a rate call: the whole batch on
+  // the GENERAL walk kernel (its map instantiation; neither speed-up form writes a map), kernels in sequence on the caller's stream
+  int64_t* map = nullptr;
   bool ahead_req = false;      // spx_batch_run_ahead: pipelined with the plan's previous call where the shape allows
   bool overlap_req = false;    // spx_batch_run_overlapped: ... and its walk kernel beside the previous call's
   void* in_ready = nullptr;    // hipEvent_t: the producers wait for it (the caller's "input is there")

@@ -129,10 +129,11 @@ Layout layout_for(const SpxPlanDev& d, const spx_stream_job* jobs, int n) {
 // (n_c = n_in for the last chunk), starts where chunk c-1 stopped (frame_begin) and carries the state record.
 // Fills tables, judges nothing: the jobs have passed spx_check_jobs at the call's top.
 static void build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n, int nch,
-                          std::vector<SpxStreamDev>& v, std::vector<int>& tiles_per_chunk, const SpxRateCall* rc = nullptr) {
+                          std::vector<SpxStreamDev>& v, std::vector<int>& tiles_per_chunk, const SpxRateCall* rc = nullptr,
+                          bool with_map = false) {
   v.resize((size_t)n * nch);
   tiles_per_chunk.assign(nch, 0);
-  int64_t fo = 0;
+  int64_t fo = 0, map_row = 0;
   const int TF = d.tile_frames;
   for (int i = 0; i < n; i++) {
     const spx_stream_job& j = jobs[i];
@@ -157,8 +158,10 @@ static void build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n
       s.first_tile = tiles_per_chunk[c];
       tiles_per_chunk[c] += (int)((T - Tprev + TF - 1) / TF);
       Tprev = T;
+      if (with_map) s.map_row = (int32_t)map_row;   // (spx_batch_run_map has refused a table of 2^31 rows or more)
     }
     fo += Ttot;
+    map_row += spx_map_rows(d, j.n_in, nonlinear);
   }
 }
 
@@ -452,7 +455,9 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
              bool do_w, const SpxCallOpts& opt) {
   const SpxForce* force = opt.force;
   // the choke point every call passes: a table that is refused has changed nothing of the plan and enqueued nothing
-  if (spx_check_jobs(plan, jobs, n, opt.rate != nullptr, force && force->no_exclusive)) return -1;
+  // (general: the call runs on the general walk kernel whatever its speeds -- a rate call, a call with a time map)
+  const bool general = opt.rate != nullptr || opt.map != nullptr;
+  if (spx_check_jobs(plan, jobs, n, general, force && force->no_exclusive)) return -1;
   SpxRange range_(do_a && do_w ? "spx_batch_run" : (do_a ? "spx_batch_analyze" : "spx_batch_walk"));
   SpxPlanDev d = plan->dev;  // a copy: the tile size is chosen per call
   Layout L = layout_for(d, jobs, n);
@@ -460,7 +465,8 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   const SpxSpeedClass SC = speed_class(jobs, n);
   const int maxC = SC.maxC;
   // (a rate call: SPX_F_NO_TRUNC is the general walk kernel's -- neither speed-up form knows it -- so the whole call is the general kernel's)
-  const bool speedup_only = SC.speedup_only && !opt.rate, any_speed = SC.any_speed && !opt.rate;
+  // (a time map: written by the general kernel's map instantiation alone -- the same rule)
+  const bool speedup_only = SC.speedup_only && !general, any_speed = SC.any_speed && !general;
   std::lock_guard<std::mutex> plan_lock(plan->mu);
   // a call that is not a sub-batch of run_split's leaves no split record for its workspace (spx_batch_analyze / _walk and mixed
   // calls come here directly: a stale record made spx_batch_read_steps look for sub-batch slices -- ADVICE r5)
@@ -485,7 +491,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   S.force_total_streams = force ? force->total_streams : n;
   S.ahead_req = opt.ahead_req; S.overlap_req = opt.overlap_req;
   SpxModeEnv E = mode_env();
-  if (opt.rate) E.concurrent_enabled = false;   // a rate call's kernels run in sequence on the caller's stream (the rate kernel ends it)
+  if (general) E.concurrent_enabled = false;   // a rate call's kernels run in sequence on the caller's stream (the rate kernel ends it); a map call's too
   SpxModeRuntime T;
   memset(&T, 0, sizeof(T));
   const int two_back = (plan->ahead_calls + SPX_RING - 2) % SPX_RING;
@@ -528,8 +534,11 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   // ---- execute ----
   std::vector<SpxStreamDev> sv;
   std::vector<int> tiles;
-  build_streams(d, jobs, n, nch, sv, tiles, opt.rate);
+  build_streams(d, jobs, n, nch, sv, tiles, opt.rate, opt.map != nullptr);
   if (opt.rate && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_rate: internal: not a plain call in sequence");
+  if (opt.map && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force || opt.rate)) return fail(-1, "spx_batch_run_map: internal: not a plain call in sequence");
+  if (opt.map && (R.walk.fast_kernel || spx_walk_config(d, {.n_streams = n, .max_channels = maxC}).mode != 0))
+    return fail(-1, "spx_batch_run_map: internal: no general walk kernel for this batch");
   unsigned char* w = static_cast<unsigned char*>(ws);
   SpxStreamDev* dstreams = reinterpret_cast<SpxStreamDev*>(w + L.off_streams);
   SpxStreamState* states = reinterpret_cast<SpxStreamState*>(w + L.off_states);
@@ -673,7 +682,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
         const SpxWalkAsk ask = {.n_streams = n, .max_channels = maxC, .speedup_only = speedup_only, .any_speed = any_speed, .lean = M.launch_lean,
                                 .short_window = short_window_res || (!force && M.walk2 && !M.launch_lean && maxC > 1)};
         spx_launch_walk(d, ask, dj, in, out, opt.rate ? opt.rate->d_tsm_n : n_out, states, scratch, (concurrent || ahead) ? d_ready : nullptr,
-                        (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, stw);
+                        (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, stw, opt.map);
       }
       if (opt.rate && c == nch - 1) {   // the rate stage: TSM buffer -> the caller's out, final counts -> n_out
         SpxTimed tm(timed, 3, stw);

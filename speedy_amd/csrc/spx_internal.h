@@ -109,7 +109,7 @@ struct SpxStreamDev {
   int32_t tension_to;    // SPX_F_TENSION_RANGE: compute tension frames [tension_skip, tension_to)
   int32_t handed_in;     // SPX_F_HANDED_IN: ring buffers handed to the TSM stage before this job ...
   int32_t ring_bufs;     // ... and complete ring buffers that exist (n_in is the TSM input's length there, not the ring's)
-  int32_t pad4;
+  int32_t map_row;       // spx_batch_run_map: index of this stream's row 0 in the call's time map (read by spx_walk_map_kernel only)
 };
 
 // TSM-stage state (libsonic's stream struct) in absolute stream coordinates.
@@ -222,7 +222,8 @@ struct SpxKernelChoice {
 // parameter added to a kernel stops the build at the selector, and then at every launch, as a direct launch would.
 using SpxAnalysisArgs = void(SpxPlanDev, const SpxStreamDev*, int, const int16_t*, SpxFrameRec*, SpxTapsDev, const int*, int*, const float*, int);
 using SpxWalkArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, int, const int*);
-using SpxWalkFastArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, const int*, int);
+using SpxWalkMapArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, int, const int*, int64_t*);
+using SpxWalkFastArgs =void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, const int*, int);
 template <typename F> struct SpxLaunch;
 template <typename... P> struct SpxLaunch<void(P...)> {
   static void go(const SpxKernelChoice& k, int grid, size_t lds, hipStream_t st, P... p) {
@@ -253,9 +254,10 @@ struct SpxWalkAsk {
   bool short_window = false;
 };
 // lds_min: the caller wants the workgroups ONE to a CU (it asks for more than half a CU's LDS, spx_engine.hip); 0 otherwise
+// map: DEVICE, the call's time map (spx_batch_run_map: the general kernel's map instantiation, SpxStreamDev::map_row), or null
 void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStreamDev* streams, const int16_t* in, int16_t* out,
                      int64_t* n_out, SpxStreamState* states, const float* scratch, const int* speed_ready, size_t lds_min,
-                     hipStream_t st);
+                     hipStream_t st, int64_t* map = nullptr);
 // mono: every stream of the launch has one channel (the 16 kHz 16-frame instantiation then reads its samples from global memory and
 // asks for no staged span)
 size_t spx_analysis_lds_bytes(const SpxPlanDev& P, bool mono);
@@ -276,6 +278,7 @@ struct SpxWalkConfig {
 };
 SpxWalkConfig spx_walk_config(const SpxPlanDev& P, const SpxWalkAsk& ask);
 SpxKernelChoice spx_walk_select(int nw, int mode);   // spx_walk.hip: the general kernel, waves per stream and mode
+SpxKernelChoice spx_walk_map_select(int nw);         // ... and its instantiation that writes a time map (mode 0)
 // spx_walk_fast.hip
 size_t spx_walk_fast_lds_bytes(const SpxPlanDev& P, int wcap);
 bool spx_walk_fast_supports(const SpxPlanDev& P, int nwm);

@@ -1,0 +1,148 @@
+// Time map of a batch call (include/speedy_hip.h: spx_plan_map_rows, spx_batch_run_map, spx_map_lookup): which output frame each
+// 10 ms of input lands on.
+//
+// The rows come from the general walk kernel's map instantiation (spx_walk.hip, spx_walk_map_kernel): row k of a nonlinear job is
+// the number of frames the time-scale stage has produced when ring buffer k -- input frames [kB, (k+1)B) -- is about to be handed
+// to it, the last row is the job's final count; a linear job has the final count alone.  spx_batch_run_map is spx_batch_run with
+// SpxCallOpts::map set (run_impl: the whole batch on the general kernel, kernels in sequence on the caller's stream).
+//
+// The lookup kernel interpolates between the nodes in exact int64 arithmetic:
+//   R = complete ring buffers of a nonlinear job (0 for a linear one)
+//   R >= 1:  X = [0, B, .., (R-1)B, n_in],  Y = the stream's R + 1 rows
+//   R == 0:  X = [0, n_in],                 Y = [0, the one row]
+// One thread per query, grid over (query block, stream); the query counts live in device memory (q_off), so the grid has a fixed
+// width and a thread strides over its stream's queries.  Forward: the segment is t / B, one division.  Inverse: a binary search
+// over the stream's rows for the last node at or below u -- about ten dependent 8-byte loads for a 10 s stream, all of them in
+// the 8 KB the stream's rows occupy, which the queries of a block share through the cache; no LDS staging (nothing measured
+// that would justify it).
+#include "spx_engine.h"
+
+#define SPX_MAP_THREADS 256
+
+// What the lookup kernel knows of a stream (HOST table in pinned memory, read once per block through the scalar cache).
+struct SpxMapStream {
+  int64_t n_in;
+  int64_t row0;   // index of the stream's first row in `map`
+  int64_t R;      // nodes = R + 1 (R >= 1) or 2 (R == 0)
+};
+
+__global__ void __launch_bounds__(SPX_MAP_THREADS)
+spx_map_lookup_kernel(const SpxMapStream* __restrict__ streams, int stream0, int B, const int64_t* __restrict__ map,
+                      const int64_t* __restrict__ q_off, const int64_t* __restrict__ q, int64_t* __restrict__ r, int inverse) {
+  const int s = stream0 + (int)blockIdx.y;
+  const SpxMapStream S = streams[s];
+  const int64_t q0 = q_off[s], q1 = q_off[s + 1];
+  const int64_t* __restrict__ rows = map + S.row0;
+  const int64_t n_in = S.n_in, R = S.R;
+  const int64_t L = R >= 1 ? R + 1 : 2;                  // nodes
+  const int64_t y_last = R >= 1 ? rows[R] : rows[0];
+  const int64_t stride = (int64_t)gridDim.x * SPX_MAP_THREADS;
+  for (int64_t i = q0 + (int64_t)blockIdx.x * SPX_MAP_THREADS + threadIdx.x; i < q1; i += stride) {
+    int64_t v = q[i], ans;
+    if (!inverse) {
+      if (v < 0) v = 0;
+      if (v > n_in) v = n_in;
+      if (n_in == 0) {
+        ans = 0;
+      } else {
+        int64_t j = v / B;
+        if (j > L - 2) j = L - 2;
+        const int64_t x0 = j * B, x1 = (j + 1 < L - 1) ? (j + 1) * B : n_in;   // (x1 - x0 >= B, or n_in > 0 where R == 0)
+        const int64_t y0 = R >= 1 ? rows[j] : 0, y1 = R >= 1 ? rows[j + 1] : y_last;
+        ans = y0 + (v - x0) * (y1 - y0) / (x1 - x0);
+      }
+    } else {
+      if (v < 0) v = 0;
+      if (v >= y_last) {
+        ans = n_in;
+      } else {
+        // the largest node index with Y <= v: Y[0] = 0 <= v < Y[L - 1]; a flat run resolves to its last node
+        int64_t lo = 0, hi = L - 1;
+        while (hi - lo > 1) {
+          const int64_t mid = (lo + hi) >> 1;
+          const int64_t ym = R >= 1 ? rows[mid] : (mid == 0 ? 0 : y_last);
+          if (ym <= v) lo = mid; else hi = mid;
+        }
+        const int64_t x0 = lo * B, x1 = (lo + 1 < L - 1) ? (lo + 1) * B : n_in;
+        const int64_t y0 = R >= 1 ? rows[lo] : 0, y1 = R >= 1 ? rows[lo + 1] : y_last;
+        // (rows that do not rise -- those of a job whose count came back negative are unspecified -- never divide by zero)
+        ans = y1 > y0 ? x0 + (v - y0) * (x1 - x0) / (y1 - y0) : x0;
+      }
+    }
+    r[i] = ans;
+  }
+}
+
+// One of the plan's two pinned staging slots (spx_engine.hip stage_tables has the protocol: a slot is rewritten only after a host
+// wait for the kernel that last read it), filled with `bytes` from `src`.  Under the plan's mutex.
+static int map_stage(spx_plan* plan, const void* src, size_t bytes, SpxStage** slot) {
+  SpxStage& G = plan->stage[plan->stage_next];
+  plan->stage_next ^= 1;
+  if (G.done) HIPCHK(hipEventSynchronize(G.done));
+  else HIPCHK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
+  if (G.cap < bytes) {
+    if (G.p) (void)hipHostFree(G.p);
+    G.p = nullptr; G.cap = 0;
+    const size_t cap = bytes * 2 + 4096;
+    HIPCHK(hipHostMalloc(&G.p, cap, hipHostMallocDefault));
+    G.cap = cap;
+  }
+  memcpy(G.p, src, bytes);
+  *slot = &G;
+  return 0;
+}
+
+extern "C" {
+
+int64_t spx_plan_map_rows(spx_plan_t plan, int64_t n_in, float nonlinear) {
+  if (!plan || n_in < 0) { fail(-1, "spx_plan_map_rows: bad arguments"); return -1; }
+  return spx_map_rows(plan->dev, n_in, nonlinear != 0.0f);
+}
+
+int spx_batch_run_map(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out,
+                      int64_t* map, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
+  // what spx_batch_run refuses, with its messages, before anything else is looked at
+  if (spx_check_jobs(plan, jobs, n, true)) return -1;
+  if (!map) return fail(-1, "spx_batch_run_map: map is NULL");
+  if (!in || !out || !n_out) return fail(-1, "spx_batch_run_map: bad arguments");
+  int64_t rows = 0;
+  for (int i = 0; i < n; i++) rows += spx_map_rows(plan->dev, jobs[i].n_in, jobs[i].nonlinear != 0.0f);
+  if (rows > 0x7fffffff) return fail(-1, "spx_batch_run_map: more than 2^31 - 1 map rows in one call");
+  SpxCallOpts o;
+  o.map = map;
+  return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, o);
+}
+
+int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n, const int64_t* map, const int64_t* q_off, const int64_t* q,
+                   int64_t* r, int inverse, void* hs) {
+  if (spx_check_jobs(plan, jobs, n, true)) return -1;
+  if (!map || !q_off || !q || !r) return fail(-1, "spx_map_lookup: bad arguments");
+  const int B = plan->dev.B;
+  std::vector<SpxMapStream> tab((size_t)n);
+  int64_t row = 0;
+  for (int i = 0; i < n; i++) {
+    const bool nonlinear = jobs[i].nonlinear != 0.0f;
+    tab[i].n_in = jobs[i].n_in;
+    tab[i].row0 = row;
+    tab[i].R = nonlinear ? jobs[i].n_in / B : 0;
+    row += spx_map_rows(plan->dev, jobs[i].n_in, nonlinear);
+  }
+  hipStream_t st = static_cast<hipStream_t>(hs);
+  std::lock_guard<std::mutex> plan_lock(plan->mu);
+  SpxStage* G = nullptr;
+  if (map_stage(plan, tab.data(), sizeof(SpxMapStream) * (size_t)n, &G)) return -2;
+  // query blocks per stream: the counts are the device's to know -- enough blocks to fill the device for a few streams, a
+  // handful for many (a thread strides over what is left)
+  int gx = 4096 / n;
+  gx = gx < 4 ? 4 : (gx > 1024 ? 1024 : gx);
+  for (int s0 = 0; s0 < n; s0 += 65535) {   // (the grid's second dimension holds 65 535)
+    const int m = n - s0 < 65535 ? n - s0 : 65535;
+    hipLaunchKernelGGL(spx_map_lookup_kernel, dim3((unsigned)gx, (unsigned)m), dim3(SPX_MAP_THREADS), 0, st,
+                       static_cast<const SpxMapStream*>(G->p), s0, B, map, q_off, q, r, inverse);
+  }
+  HIPCHK(hipEventRecord(G->done, st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

@@ -73,6 +73,7 @@ extern "C" void spx_debug_stamps(unsigned long long* out, int reset) {
 
 struct WalkCtx {
   int* flush_rem;     // SPX_F_NO_TRUNC: where the flush leaves {frames the stage held, frames produced so far} (nullptr: truncate as usual)
+  int64_t* map;       // time map (spx_walk_map_kernel): the stream's rows, row k = frames produced when ring buffer k is handed over (nullptr: none)
   const int16_t* in;  // stream input (interleaved)
   int16_t* out;       // stream output
   pos_t out_cap;
@@ -665,11 +666,15 @@ static __host__ __device__ inline WalkLds walk_lds_layout(const SpxPlanDev& P, i
   return L;
 }
 
-template <int NW, int FAST>
-__global__ void __launch_bounds__(64 * NW)
-spx_walk_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const int16_t* __restrict__ in_base,
-                int16_t* __restrict__ out_base, int64_t* __restrict__ n_out, SpxStreamState* __restrict__ states,
-                const float* scratch_base, int maxC, const int* speed_ready) {
+// The body of the walk kernels.  MAP (spx_walk_map_kernel, FAST == 0 only): the stream's time-map rows are written as the events
+// go by -- everything that belongs to the map sits behind `if constexpr (MAP)`, so spx_walk_kernel's instantiations compile from
+// the code they always compiled from.
+template <int NW, int FAST, bool MAP>
+__device__ __forceinline__ void
+walk_body(const SpxPlanDev& P, const SpxStreamDev* __restrict__ streams, const int16_t* __restrict__ in_base,
+          int16_t* __restrict__ out_base, int64_t* __restrict__ n_out, SpxStreamState* __restrict__ states,
+          const float* scratch_base, int maxC, const int* speed_ready, int64_t* __restrict__ map_base) {
+  static_assert(!MAP || FAST == 0, "the time map is the general kernel's");
   constexpr int NT = 64 * NW;
   // the walk is the latency-critical chain: where the analysis kernel shares a SIMD, these waves issue first
   __builtin_amdgcn_s_setprio(3);
@@ -703,6 +708,8 @@ spx_walk_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const in
   // ---------------------------------- TSM stage context ----------------------------------
   WalkCtx X;
   X.flush_rem = (S.flags & SPX_F_NO_TRUNC) ? &states[blockIdx.x].flush_remaining : nullptr;
+  X.map = nullptr;
+  if constexpr (MAP) X.map = map_base ? map_base + S.map_row : nullptr;
   X.in = in_base + S.in_off - S.tsm_shift * S.channels;  // indexed by TSM position (= input frame + flush padding so far)
   X.out = out_base + S.out_off;
   X.out_cap = (pos_t)(S.out_cap > 0x7fffffff ? 0x7fffffff : S.out_cap);
@@ -813,6 +820,11 @@ spx_walk_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const in
           avail += 2 * P.maxRequired;
         }
         STAMP(0);
+        if constexpr (MAP) {
+          // ring buffer `ev` is about to be handed over: the frames produced so far are its row (one 8-byte store per 10 ms of
+          // input, never waited for; a linear job's one event has no row of its own)
+          if (X.map && nl != 0.0f && ev < ev1 && tid == 0) X.map[ev] = (int64_t)st.out_n;
+        }
         tsm_process<NW, FAST>(P, X, st, curSpeed, avail);
         STAMP(12);
         if (ev >= ev1) {
@@ -834,7 +846,27 @@ spx_walk_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const in
     states[blockIdx.x].curSpeed = curSpeed;
     if (nl != 0.0f) states[blockIdx.x].handed = (int)handed;
     if (n_out) n_out[blockIdx.x] = st.overflow == 2 ? INT64_MIN : (st.overflow ? -(int64_t)st.out_n : (int64_t)st.out_n);
+    if constexpr (MAP) {
+      // the last row: the job's final count, behind flush and truncation (a linear job's only row)
+      if (X.map && do_flush) X.map[nl != 0.0f ? S.n_in / B : 0] = st.overflow == 2 ? INT64_MIN : (st.overflow ? -(int64_t)st.out_n : (int64_t)st.out_n);
+    }
   }
+}
+
+template <int NW, int FAST>
+__global__ void __launch_bounds__(64 * NW)
+spx_walk_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const int16_t* __restrict__ in_base,
+                int16_t* __restrict__ out_base, int64_t* __restrict__ n_out, SpxStreamState* __restrict__ states,
+                const float* scratch_base, int maxC, const int* speed_ready) {
+  walk_body<NW, FAST, false>(P, streams, in_base, out_base, n_out, states, scratch_base, maxC, speed_ready, nullptr);
+}
+// The general kernel with a time map (spx_batch_run_map): row k of a stream at map_base[streams[i].map_row + k].
+template <int NW>
+__global__ void __launch_bounds__(64 * NW)
+spx_walk_map_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const int16_t* __restrict__ in_base,
+                    int16_t* __restrict__ out_base, int64_t* __restrict__ n_out, SpxStreamState* __restrict__ states,
+                    const float* scratch_base, int maxC, const int* speed_ready, int64_t* __restrict__ map_base) {
+  walk_body<NW, 0, true>(P, streams, in_base, out_base, n_out, states, scratch_base, maxC, speed_ready, map_base);
 }
 
 // Which kernel variant a batch gets: 0 general, 1 speed-up mono, 2 speed-up multi-channel.  FAST: all streams speeding
@@ -930,6 +962,12 @@ SpxKernelChoice spx_walk_select(int nw, int mode) {
   return mode == 1 ? WALK_K(4, 1) : mode == 2 ? WALK_K(4, 2) : WALK_K(4, 0);
 #undef WALK_K
 }
+// ... and of the general kernel that writes a time map (mode 0 only: the speed-up forms have none).
+SpxKernelChoice spx_walk_map_select(int nw) {
+  static_assert(std::is_same<decltype(spx_walk_map_kernel<8>), SpxWalkMapArgs>::value, "SpxWalkMapArgs is the kernel's argument list");
+  if (nw == 8) return SpxKernelChoice{"spx_walk_map_kernel", reinterpret_cast<const void*>(spx_walk_map_kernel<8>), 64 * 8, 1, {8}};
+  return SpxKernelChoice{"spx_walk_map_kernel", reinterpret_cast<const void*>(spx_walk_map_kernel<4>), 64 * 4, 1, {4}};
+}
 int spx_walk_vgprs(const SpxPlanDev& P, const SpxWalkAsk& ask, int* scratch_bytes) {
   return spx_kernel_vgprs(spx_walk_config(P, ask).kernel.fn, scratch_bytes);
 }
@@ -942,11 +980,19 @@ extern "C" int spx_debug_last_walk_form(void) { return g_last_walk_form.load(std
 
 void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStreamDev* streams, const int16_t* in, int16_t* out,
                      int64_t* n_out, SpxStreamState* states, const float* scratch, const int* speed_ready, size_t lds_min,
-                     hipStream_t st) {
+                     hipStream_t st, int64_t* map) {
   const int n_streams = ask.n_streams;
   if (n_streams <= 0) return;
   const int maxC = ask.max_channels < 1 ? 1 : ask.max_channels;
   const SpxWalkConfig cfg = spx_walk_config(P, ask);
+  if (map) {
+    // a time map: the general kernel's own instantiation, same waves and LDS.  (run_impl has refused a map call whose shape asks
+    // for a speed-up form before it enqueued anything: there is no such kernel, and none is launched in its place.)
+    if (cfg.fast_kernel || cfg.mode != 0) return;
+    g_last_walk_form.store(0, std::memory_order_relaxed);
+    SpxLaunch<SpxWalkMapArgs>::go(spx_walk_map_select(cfg.nw), n_streams, cfg.lds, st, P, streams, in, out, n_out, states, scratch, maxC, speed_ready, map);
+    return;
+  }
   g_last_walk_form.store(cfg.fast_kernel ? 16 * cfg.nwm + cfg.nwc : 0, std::memory_order_relaxed);
   static const bool dbg_mode = getenv("SPX_DEBUG_MODE") != nullptr;
   if (dbg_mode) fprintf(stderr, "[spx walk] rate %d n %d maxC %d: %s %d + %d waves, window %d frames, %zu B LDS per stream (at least %zu asked)\n", P.rate, n_streams, maxC,
