@@ -1,0 +1,414 @@
+"""CPU: everything that turns a chosen period into int16 output -- cross-fade, copy-through and its cap, `remaining` carried across
+a speed change, unity pass-through, a failed step, the flush, the whole rate stage -- against an exact integer definition
+(tests/tsm_ref.py) on inputs that give it teeth (tests/tsm_inputs.py: full scale, channel-distinct).
+
+The oracle's TSM API (orc_sonicInt*) equals the definition sample for sample after EVERY call; the oracle shim's nonlinear stream
+hands the TSM stage the closed-form event list and its output is the definition's on that list; the census conditions are
+requirements on the inputs, asserted from the definition alone; every switch of the definition (one mistake each) changes the
+output of some directed input.  All comparisons are integer equality.
+
+SPX_TSM_CENSUS=<path> writes the census table (profiles/tsm_definition.txt).
+"""
+import os
+
+import numpy as np
+import pytest
+
+import tsm_inputs as I
+import tsm_ref as T
+
+
+# ------------------------------------------------------------------ the definition, once ------------------------------------------------------------------
+
+def _run_events(make, events):
+    """A stream of the definition over an event list: (stream, frames produced after each call)."""
+    s = make()
+    counts = []
+    for ev in events:
+        if ev[0] == "write":
+            s.write(ev[1], ev[2])
+        else:
+            s.flush(ev[1])
+        counts.append(s.frames_out)
+    return s, counts
+
+
+def _first_life(events):
+    k = [e[0] for e in events].index("flush")
+    return events[:k + 1]
+
+
+@pytest.fixture(scope="module")
+def linear():
+    """{name: the definition's stream} of every directed linear job; computed once, left unchanged."""
+    return {name: T.linear_job(x, rate, ch, speed) for name, rate, ch, x, speed in I.linear_jobs()}
+
+
+@pytest.fixture(scope="module")
+def rated():
+    return {name: T.rate_job(x, hz, ch, speed, rate) for name, hz, ch, x, speed, rate in I.rate_jobs()}
+
+
+@pytest.fixture(scope="module")
+def planted():
+    return {name: _run_events(lambda: T.SpeedStream(rate, ch), ev) for name, rate, ch, ev in I.planted_streams()}
+
+
+def _shim_stream(orc, x, rate, ch, speed, nl):
+    """The oracle shim's stream in writes of 1000 frames: (output, [(speed, buffer)] of its handoff callback)."""
+    L = orc.lib()
+    events = []
+
+    def on(s, t, sp, buf, frames):
+        events.append((float(np.float32(sp)), np.ctypeslib.as_array(buf, shape=(frames * ch,)).copy()))
+    cb = orc.HANDOFF_FN(on)
+    h = L.orc_sonicCreateStream(rate, ch, 0)
+    L.orc_sonicSetSpeed(h, speed); L.orc_sonicEnableNonlinearSpeedup(h, nl); L.orc_sonicSetDurationFeedbackStrength(h, 0.0)
+    L.orc_sonicHandoffCallback(h, cb)
+    buf, got = np.zeros((1 << 17) * ch, np.int16), []
+
+    def drain():
+        while True:
+            k = L.orc_sonicReadShortFromStream(h, orc.sptr(buf), 1 << 17)
+            if k <= 0:
+                return
+            got.append(buf[:k * ch].copy())
+    n = x.size // ch
+    for pos in range(0, n, 1000):
+        seg = np.ascontiguousarray(x[pos * ch:(pos + 1000) * ch])
+        assert L.orc_sonicWriteShortToStream(h, orc.sptr(seg), seg.size // ch) == 1
+        drain()
+    assert L.orc_sonicFlushStream(h) == 1
+    drain()
+    L.orc_sonicDestroyStream(h)
+    return (np.concatenate(got) if got else np.zeros(0, np.int16)), events
+
+
+@pytest.fixture(scope="module")
+def nonlinear(orc):
+    """{name: (shim output, handoff events, the definition's stream on those events)}"""
+    out = {}
+    for name, rate, ch, x, speed, nl in I.nonlinear_jobs():
+        ref, events = _shim_stream(orc, x, rate, ch, speed, nl)
+        s = T.nonlinear_job(x, rate, ch, [sp for sp, _ in events], speed)
+        out[name] = (ref, events, s)
+    return out
+
+
+# ------------------------------------------------------------------ the inputs ------------------------------------------------------------------
+
+def test_the_directed_inputs_are_full_scale_bounded_and_cover_every_speed():
+    for name, rate, ch, x, speed in I.linear_jobs():
+        assert x.dtype == np.int16 and x.size // ch <= 1.0 * rate, name
+        if name.startswith(("channels", "rates", "speeds")):
+            assert 0.3 * rate - 1 <= x.size // ch, name
+            assert x.max() == 32767 and x.min() == -32768, name
+    lo, hi = I.unity_neighbours()
+    assert T.is_unity(lo) and not T.is_unity(hi) and np.nextafter(np.float32(lo), np.float32(2)) == np.float32(hi)
+    assert T.is_unity(1.0) and not T.is_unity(1.00002) and not T.is_unity(0.99998)
+    assert I.below(2.0) < 2.0 and np.float32(I.below(2.0)) == np.nextafter(np.float32(2), np.float32(0))
+    for name, rate, ch, ev in I.planted_streams():
+        kinds = [e[0] for e in ev]
+        assert name.startswith("second_life") or sorted(set(e[-1] for e in ev)) == sorted(set(
+            I.SEQUENCE if "near_unity" in name else I.SEQUENCE_UP if name.startswith("speedup") else I.SEQUENCE_FAR)), name                  # every speed of the sequence is used
+        assert kinds.count("flush") == 2 and kinds[-1] == "flush" and "write" in kinds[kinds.index("flush"):], name     # a second life
+        assert sum(e[1].size for e in ev if e[0] == "write") // ch <= rate, name
+
+
+def test_no_two_channels_of_an_output_are_equal(linear, rated):
+    """A permuted channel or a slipped e / C in a kernel cannot hide behind equal channels."""
+    seen = 0
+    for name, rate, ch, x, speed in I.linear_jobs():
+        if ch > 1:
+            y = np.asarray(linear[name].out, np.int64).reshape(-1, ch)
+            assert y.shape[0] > 1000, name
+            for a in range(ch):
+                for b in range(a + 1, ch):
+                    assert not np.array_equal(y[:, a], y[:, b]), (name, a, b)
+            seen += 1
+    assert seen >= 20
+    for name, hz, ch, x, speed, rate in I.rate_jobs():
+        if ch > 1 and x.size // ch > 100:            # (the three-frame stream lies inside every channel's first rectangle)
+            y = np.asarray(rated[name].out, np.int64).reshape(-1, ch)
+            for a in range(ch):
+                for b in range(a + 1, ch):
+                    assert not np.array_equal(y[:, a], y[:, b]), (name, a, b)
+
+
+# ------------------------------------------------------------------ the oracle's TSM API ------------------------------------------------------------------
+
+class _Int:
+    """The oracle's orc_sonicInt* stream; read() drains it."""
+
+    def __init__(self, orc, rate, ch, playback=None):
+        self.orc, self.L, self.ch = orc, orc.lib(), ch
+        self.h = self.L.orc_sonicIntCreateStream(rate, ch)
+        assert self.h
+        if playback is not None:
+            self.L.orc_sonicIntSetRate(self.h, playback)
+        self.buf = np.zeros((1 << 16) * ch, np.int16)
+
+    def read(self):
+        got = []
+        while True:
+            k = self.L.orc_sonicIntReadShortFromStream(self.h, self.orc.sptr(self.buf), 1 << 16)
+            if k <= 0:
+                return np.concatenate(got).astype(np.int64) if got else np.zeros(0, np.int64)
+            got.append(self.buf[:k * self.ch].copy())
+
+    def call(self, ev):
+        self.L.orc_sonicIntSetSpeed(self.h, ev[-1])
+        if ev[0] == "write":
+            x = np.ascontiguousarray(ev[1], np.int16)
+            assert self.L.orc_sonicIntWriteShortToStream(self.h, self.orc.sptr(x), x.size // self.ch) == 1
+        else:
+            assert self.L.orc_sonicIntFlushStream(self.h) == 1
+        return self.read()
+
+    def close(self):
+        self.L.orc_sonicIntDestroyStream(self.h)
+
+
+def _call_for_call(orc, rate, ch, events, out, counts, tag, playback=None):
+    """The oracle stream's reads after every call equal the definition's output of that call."""
+    o = _Int(orc, rate, ch, playback)
+    want = np.asarray(out, np.int64)
+    done = 0
+    for k, ev in enumerate(events):
+        got = o.call(ev)
+        # (a flush may cut, but never below what the calls before it produced: expected >= out)
+        end = counts[k] * ch
+        assert got.size == end - done, (tag, k, ev[0], ev[-1], got.size // ch, (end - done) // ch)
+        assert np.array_equal(got, want[done:end]), (tag, k, ev[0], ev[-1], int(np.nonzero(got != want[done:end])[0][0]))
+        done = end
+    o.close()
+    assert done == want.size, tag
+
+
+def test_oracle_equals_the_definition_on_every_directed_batch_job(orc, linear):
+    for name, rate, ch, x, speed in I.linear_jobs():
+        s = linear[name]
+        _call_for_call(orc, rate, ch, [("write", x, speed), ("flush", speed)], s.out, [s.frames_after_write, s.frames_out], name)
+
+
+def test_oracle_equals_the_definition_on_the_planted_event_lists(orc, planted):
+    for name, rate, ch, ev in I.planted_streams():
+        s, counts = planted[name]
+        assert (s.steps > 15 or name.startswith("second_life") or "near_unity" in name) and counts[-1] > 0, (name, s.steps)
+        _call_for_call(orc, rate, ch, ev, s.out, counts, name)
+
+
+def test_oracle_equals_the_definition_on_the_rate_jobs(orc, rated):
+    for name, hz, ch, x, speed, rate in I.rate_jobs():
+        s = rated[name]
+        _call_for_call(orc, hz, ch, [("write", x, speed), ("flush", speed)], s.out, [s.frames_after_write, s.frames_out], name, rate)
+
+
+@pytest.mark.parametrize("rate", [1.25, 0.8, 3.0])
+def test_oracle_equals_the_definition_on_a_planted_first_life_with_a_rate(orc, rate):
+    """One life cycle of every planted event list (up to its first flush) with a playback rate, call for call."""
+    for name, hz, ch, ev in I.planted_streams():
+        ev = _first_life(ev)
+        s, counts = _run_events(lambda: T.RateStream(hz, ch, rate), ev)
+        assert counts[-1] > 1000 or name.startswith("second_life"), name
+        _call_for_call(orc, hz, ch, ev, s.out, counts, (name, rate), rate)
+
+
+# ------------------------------------------------------------------ the oracle shim's nonlinear stream ------------------------------------------------------------------
+
+def test_the_shims_handoff_has_the_closed_form_shape_and_the_definition_gives_its_output(orc, nonlinear):
+    """n_in // B events of B frames, x[k B : (k + 1) B], the trailing partial buffer dropped; the first K events at the K values of
+    the speed tap, the later ones at the last of them (tsm_ref.event_speeds).  Every stream with an event below speed 2 has events
+    that inherit a pending copy from an event of another speed."""
+    for name, rate, ch, x, speed, nl in I.nonlinear_jobs():
+        ref, events, s = nonlinear[name]
+        B = rate // 100
+        n = x.size // ch
+        assert len(events) == n // B and n % B != 0, name
+        for k, (_, b) in enumerate(events):
+            assert np.array_equal(b, x[k * B * ch:(k + 1) * B * ch]), (name, k)
+        speeds = [sp for sp, _ in events]
+        assert len(set(speeds)) > 10, name
+        # the speeds: the first K events carry the speed tap's K values, the later ones the last of them
+        tap = orc.compress_sound(x, rate, ch, speed, nl, 0.0, False, chunk=1000, taps=True)["speed"]
+        assert 10 < len(tap) < len(events), (name, len(tap), len(events))
+        assert speeds == T.event_speeds(n, rate, tap, speed), name
+        assert speeds[:len(tap)] == [float(v) for v in tap] and set(speeds[len(tap):]) == {float(tap[-1])}, name
+        got = np.asarray(s.out, np.int64)
+        assert got.size == ref.size and np.array_equal(got, ref.astype(np.int64)), name
+        if min(speeds) < 2.0:          # (an event at 2 or more, or below 0.5, leaves no copy behind)
+            assert s.census["inherits_copy"] >= 1, (name, s.census)
+    assert sum(1 for _, ev, _ in nonlinear.values() if min(sp for sp, _ in ev) < 2.0) >= 4
+
+
+# ------------------------------------------------------------------ the census ------------------------------------------------------------------
+
+# the speeds at which a job cross-fades throughout (at 1.00002 and its like one period in 50 000 is cross-faded, the rest copied;
+# at 2000 and 0.0001 every step fails; at 200 most do)
+FULL_SPEEDS = tuple(s for s in I.SPEEDS if abs(s - 1.0) > 1e-3 and s not in (2000.0, 0.0001))
+
+
+def _total(streams):
+    t = dict.fromkeys(T.CENSUS, 0)
+    for s in streams:
+        for k, v in s.census.items():
+            t[k] += v
+    return t
+
+
+def test_every_full_scale_job_has_the_delicate_numerators(linear):
+    """Per full-scale job that runs cross-fades: at least 100 numerators that are negative and no multiple of n (floor and
+    truncation differ there), at least 100 with |num| >= 32000 n (the last bits of a 16-bit reciprocal, the sign of a biased sample)."""
+    for name, rate, ch, x, speed in I.linear_jobs():
+        if name.startswith(("channels", "rates")) or (name.startswith("speeds") and speed in FULL_SPEEDS):
+            c = linear[name].census
+            assert c["xfade_neg_frac"] >= 100 and c["xfade_full"] >= 100, (name, c)
+
+
+def test_every_census_condition_is_reached(linear, planted, rated):
+    """Each count of the census is at least 1 somewhere in the directed set -- from the definition alone.
+
+    Two conditions that are not obvious:
+      * a KEPT cross-fade sample with exactly one operand in the flush padding: it survives the cut at every length of the run
+        at speeds 2.0, 3.5 and 0.4, asserted below;
+      * a flush that does NOT cut is reached only where a step fails: speeds 2000 and 0.0001 (every step fails) and 200 (23 steps
+        run at 22.05 kHz before one fails) -- the write ends there, so the output stays short of `expected`.  No directed job
+        without a failed step is uncut, asserted below over all of them.  An argument, not a proof, for why: the padded process
+        call goes on while pos + maxRequired <= pending + 2 maxRequired, so it consumes all pending input and more than
+        maxRequired frames of padding, and the steps on that padding usually produce more than the 0.5 frame that `expected`
+        allows beyond pending / speed; it gives no bound per frame of padding (with maxRequired zeros instead of 2 maxRequired the
+        output does fall short: the switch flush_pad_short, caught at lengths 678 and 679 at speed 0.7).  The mutant `flush_no_cut`
+        needs no uncut flush: every job that cuts catches it."""
+    lin = _total(linear.values())
+    for k in ("xfade_neg_frac", "xfade_full", "pad_kept", "copy_capped", "failed_steps", "flush_cut", "flush_uncut", "flush_tie"):
+        assert lin[k] >= 1, (k, lin)
+    pl = _total(s for s, _ in planted.values())
+    for k in ("inherits_copy", "unity_with_remaining", "copy_capped", "flush_cut"):
+        assert pl[k] >= 1, (k, pl)
+    for name, (s, _) in planted.items():
+        if name.startswith("planted"):
+            assert s.census["inherits_copy"] >= 1 and s.census["unity_with_remaining"] >= 1, (name, s.census)
+        if name.startswith("speedup"):
+            assert s.census["inherits_copy"] >= 1 and s.census["xfade_full"] >= 100, (name, s.census)
+    rt = _total(rated.values())
+    for k in ("rate_neg_frac", "halving_dropped"):
+        assert rt[k] >= 1, (k, rt)
+    assert rated["rate/44100Hz/2ch/13230/1.3/1.1"].census["halving_dropped"] >= 1
+    for name, rate, ch, x, speed in I.linear_jobs():
+        c = linear[name].census
+        if name.startswith("run"):
+            assert (c["pad_kept"] >= 1 or speed == 0.7) and c["flush_cut"] == 1 and c["flush_uncut"] == 0, (name, c)
+        if speed in (1.3, 1.00002) and name.startswith("speeds"):
+            # (at 16 kHz and 1.3 the periods this signal yields leave copies of 2.33 periods that stay below maxRequired)
+            assert c["copy_capped"] >= 1 or rate == 16000 and speed == 1.3, (name, c)
+        if speed in (2000.0, 0.0001):
+            assert c["failed_steps"] == 2 and c["flush_uncut"] == 1, (name, c)
+        assert c["flush_uncut"] == 0 or c["failed_steps"] >= 1, (name, c)           # uncut only where a step failed
+    assert linear["speeds/22050Hz/1ch/7000/200"].steps > 20 and linear["speeds/22050Hz/1ch/7000/200"].census["flush_uncut"] == 1
+    # the exact .5 tie of the flush count: speed 2.0 with an odd pending count -- every second length of the run
+    ties = [x.size for name, rate, ch, x, speed in I.linear_jobs() if name.startswith("run") and speed == 2.0 and linear[name].census["flush_tie"]]
+    assert len(ties) == len(I.RUN) // 2, ties
+
+
+# ------------------------------------------------------------------ teeth ------------------------------------------------------------------
+
+def _linear_differs(linear, names, switch):
+    by = {j[0]: j for j in I.linear_jobs()}
+    for name in names:
+        _, rate, ch, x, speed = by[name]
+        m = T.linear_job(x, rate, ch, speed, switch)
+        if m.out != linear[name].out or m.frames_after_write != linear[name].frames_after_write:
+            return name
+    return None
+
+
+def _planted_differs(planted, switch):
+    for name, rate, ch, ev in I.planted_streams():
+        m, counts = _run_events(lambda: T.SpeedStream(rate, ch, switch), ev)
+        if m.out != planted[name][0].out or counts != planted[name][1]:
+            return name
+    return None
+
+
+_J = "channels/22050Hz/%dch/6615/%s"
+TEETH = {
+    "xfade_floor": [_J % (2, "2"), _J % (1, "0.7")],
+    "xfade_swapped": [_J % (2, "2"), _J % (1, "0.7")],
+    "xfade_late": [_J % (2, "2"), _J % (1, "0.7")],
+    "copy_uncapped": [_J % (1, "1.3"), "speeds/22050Hz/1ch/7000/1.00002"],
+    "flush_floor": ["run/22050Hz/1ch/2981/2", "run/22050Hz/1ch/2981/0.4"],
+    "flush_after_pad": [_J % (1, "2"), _J % (1, "0.7")],
+    "flush_pad_short": ["lengths/22050Hz/1ch/678/0.7", "lengths/22050Hz/1ch/679/0.7", "run/22050Hz/1ch/3019/0.7"],
+    "flush_no_cut": [_J % (1, "2"), _J % (1, "0.7")],
+}
+
+
+@pytest.mark.parametrize("switch", sorted(TEETH))
+def test_every_speed_stage_switch_changes_a_batch_jobs_output(linear, switch):
+    """Teeth: the mutant's final output (or what it had produced after the write) differs from the definition's on EVERY job
+    listed for it: a kernel with that mistake cannot produce the definition's output there."""
+    for name in TEETH[switch]:
+        assert _linear_differs(linear, [name], switch) == name, (switch, name)
+
+
+@pytest.mark.parametrize("switch", ["unity_clears_remaining", "flush_resets_prev", "copy_uncapped", "xfade_floor", "flush_floor"])
+def test_the_stream_switches_change_a_planted_event_list(planted, switch):
+    """A unity write that clears `remaining` and a flush that clears prevPeriod show only where a stream goes on: on the planted
+    event lists (unity between two other speeds; a second life)."""
+    assert _planted_differs(planted, switch) is not None, switch
+
+
+def test_unity_clears_remaining_and_flush_resets_prev_cannot_show_in_a_linear_job(linear):
+    """One write at one speed, one flush: a unity job never has a `remaining`, and nothing follows the flush.  These two switches
+    are equivalent to the definition on every linear batch job -- they are pinned by the stream API alone."""
+    names = [j[0] for j in I.linear_jobs() if j[0].startswith(("speeds", "lengths", "rates"))]
+    assert _linear_differs(linear, names, "unity_clears_remaining") is None
+    assert _linear_differs(linear, names, "flush_resets_prev") is None
+
+
+@pytest.mark.parametrize("switch", T.RATE_SWITCHES)
+def test_every_rate_stage_switch_changes_a_rate_jobs_output(rated, switch):
+    caught = []
+    for name, hz, ch, x, speed, rate in I.rate_jobs():
+        m = T.rate_job(x, hz, ch, speed, rate, switch)
+        if m.out != rated[name].out or m.frames_after_write != rated[name].frames_after_write:
+            caught.append(name)
+    assert caught, switch
+    if switch == "rate_no_halving":          # shows exactly where halving dropped a bit
+        assert "rate/44100Hz/2ch/13230/1.3/1.1" in caught
+        assert all(rated[n].census["halving_dropped"] for n in caught), caught
+
+
+def test_every_switch_has_a_test():
+    covered = set(TEETH) | {"unity_clears_remaining", "flush_resets_prev"} | set(T.RATE_SWITCHES)
+    assert covered == set(T.SWITCHES)
+
+
+# ------------------------------------------------------------------ the table ------------------------------------------------------------------
+
+def test_census_table(linear, planted, rated, nonlinear):
+    """The census of every directed input; written to SPX_TSM_CENSUS when that is set (profiles/tsm_definition.txt)."""
+    rows = []
+    for name, rate, ch, x, speed in I.linear_jobs():
+        if not name.startswith("run"):
+            rows.append((name, linear[name].frames_out, linear[name].steps, linear[name].census))
+    for sp in I.RUN_SPEEDS:
+        ss = [linear[j[0]] for j in I.linear_jobs() if j[0].startswith("run") and j[4] == sp]
+        rows.append(("run/22050Hz/1ch/%d..%d/%g (sum of %d)" % (I.RUN[0], I.RUN[-1], sp, len(ss)), sum(s.frames_out for s in ss),
+                     sum(s.steps for s in ss), _total(ss)))
+    for name, (s, _) in planted.items():
+        rows.append((name, s.frames_out, s.steps, s.census))
+    for name, (_, _, s) in nonlinear.items():
+        rows.append((name, s.frames_out, s.steps, s.census))
+    for name, s in rated.items():
+        rows.append((name, s.frames_out, s.speed_stage.steps, s.census))
+    assert all(r[3].keys() == dict.fromkeys(T.CENSUS).keys() for r in rows)
+    path = os.environ.get("SPX_TSM_CENSUS")
+    if path:
+        short = ("neg_frac", "full", "pad_kept", "capped", "inherit", "unity_rem", "failed", "cut", "uncut", "tie", "r_neg_frac", "halv_drop")
+        notes = [ln for ln in open(path)] if os.path.exists(path) else []
+        with open(path, "w") as f:
+            f.write("%-44s %7s %5s " % ("input", "frames", "steps") + " ".join("%10s" % k for k in short) + "\n")
+            for name, frames, steps, c in rows:
+                f.write("%-44s %7d %5d " % (name, frames, steps) + " ".join("%10d" % c[k] for k in T.CENSUS) + "\n")
+            f.writelines(ln for ln in notes if ln.startswith("#"))      # (the GPU file's wall time, noted by hand, stays)
