@@ -219,11 +219,11 @@ static int float_layout(spx_plan_t plan, const spx_stream_job* jobs, const float
     in_vals = std::max(in_vals, j.in_off + j.n_in * j.channels);
     out_vals = std::max(out_vals, j.out_off + j.out_cap * j.channels);
   }
-  size_t o = (FL.base + 255) & ~(size_t)255;
-  FL.off_table = o; o += (sizeof(SpxConvJob) * (size_t)n + 255) & ~(size_t)255;
-  FL.off_in = o;    o += (sizeof(int16_t) * (size_t)(in_vals + 64) + 255) & ~(size_t)255;
-  FL.off_out = o;   o += (sizeof(int16_t) * (size_t)out_vals + 255) & ~(size_t)255;
-  FL.total = o;
+  SpxCarve ws(FL.base);
+  FL.off_table = ws.take(sizeof(SpxConvJob) * (size_t)n);
+  FL.off_in = ws.take(sizeof(int16_t) * (size_t)(in_vals + 64));
+  FL.off_out = ws.take(sizeof(int16_t) * (size_t)out_vals);
+  FL.total = ws.o;
   return 0;
 }
 
@@ -283,24 +283,14 @@ int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float
   int16_t* st_out = reinterpret_cast<int16_t*>(w + FL.off_out);
 
   // ---- the table: through a per-thread pinned slot (two, taking turns), reused once the kernel that last read it has retired ----
-  static thread_local SpxStage G2[2];
-  static thread_local int g_next = 0;
-  SpxStage& G = G2[g_next];
-  g_next ^= 1;
-  const size_t need = sizeof(SpxConvJob) * (size_t)n;
-  if (G.done) HIPCHK(hipEventSynchronize(G.done));
-  else HIPCHK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
-  if (G.cap < need) {
-    if (G.p) (void)hipHostFree(G.p);
-    G.p = nullptr; G.cap = 0;
-    HIPCHK(hipHostMalloc(&G.p, need * 2 + 1024, hipHostMallocDefault));
-    G.cap = need * 2 + 1024;
-  }
+  static thread_local SpxStagePair stage;
+  SpxStage& G = stage.take();
+  if (G.acquire(sizeof(SpxConvJob) * (size_t)n)) return -2;
   int max_in = 1, max_out = 1;
   if (conv_fill(static_cast<SpxConvJob*>(G.p), jobs, n, &max_in, &max_out)) return fail(-1, "spx_batch_run_float: out_cap too large for one launch");
   SpxRange range_("spx_batch_run_float");
   conv_upload(G.p, d_tab, n, st);
-  HIPCHK(hipEventRecord(G.done, st));
+  if (G.release(st)) return -2;
 
   // ---- input conversion | the int16 call on the stagings | output conversion, all on hip_stream ----
   conv_launch_in(d_tab, n, max_in, in, st_in, st);

@@ -184,21 +184,14 @@ int spx_batch_pack_outputs(const spx_stream_job* jobs, int n, const int16_t* out
   if (hipMallocAsync(&d_tab, need, st) != hipSuccess) return fail(-2, "spx_batch_pack_outputs: allocation failed");
   // host side of the table: a per-thread pinned slot, reused once the copy that last read it has retired
   static thread_local SpxStage G;
-  if (G.done) HIPCHK(hipEventSynchronize(G.done));
-  else HIPCHK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
-  if (G.cap < need) {
-    if (G.p) (void)hipHostFree(G.p);
-    G.p = nullptr; G.cap = 0;
-    HIPCHK(hipHostMalloc(&G.p, need * 2 + 1024, hipHostMallocDefault));
-    G.cap = need * 2 + 1024;
-  }
+  if (G.acquire(need)) return -2;
   unsigned char* h = static_cast<unsigned char*>(G.p);
   int64_t* h_off = reinterpret_cast<int64_t*>(h);
   int64_t* h_cap = h_off + n;
   int* h_ch = reinterpret_cast<int*>(h + (size_t)n * 2 * sizeof(int64_t));
   for (int i = 0; i < n; i++) { h_off[i] = jobs[i].out_off; h_cap[i] = jobs[i].out_cap; h_ch[i] = jobs[i].channels; }
   HIPCHK(hipMemcpyAsync(d_tab, h, need, hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(G.done, st));
+  if (G.release(st)) return -2;
   const int64_t* d_off = reinterpret_cast<const int64_t*>(d_tab);
   const int* d_ch = reinterpret_cast<const int*>(static_cast<unsigned char*>(d_tab) + (size_t)n * 2 * sizeof(int64_t));
   hipLaunchKernelGGL(spx_pack_offsets_kernel, dim3(1), dim3(256), 0, st, n_out, d_ch, d_off + n, n, offsets);

@@ -1,9 +1,15 @@
 // Host side of the batch engine, shared by its translation units (round 6: spx_engine.hip was 1 800 lines):
 //   spx_plan.hip    plan tables (DFT spec twiddles, window, Rader), sizes and capacities
 //   spx_engine.hip  one batch call: workspace layout, staging, the library's streams, the plan's ring of earlier calls,
-//                   run_impl (decide with spx_mode.h, then launch), sub-batches
+//                   run_impl (decide with spx_mode.h, then launch), sub-batches, the rate call
 //   spx_mixed.hip   one call over several plans (BASELINE configs[4])
+//   spx_map.hip     the call with a time map, and the lookup
+//   spx_convert.hip the call on float samples: two conversions around the int16 call
+//   spx_pipeline.hip the pipeline object: it includes this header for the entries it calls (spx_internal_run*, spx_conv_*)
 //   spx_diag.hip    kernel names, resource queries, timing collection, output packing, small copies
+// What they share is declared HERE, once: the pinned staging slot and its protocol (SpxStage, SpxStagePair), the workspace carver
+// (SpxCarve), a call's arguments and options (SpxCall, SpxCallOpts), the device guard's scope (SpxGuardScope), mode_runtime (of
+// spx_choose_mode's inputs; mode_shape is spx_engine.hip's own) and taps_advance.
 // Nothing here is part of the C-ABI (include/speedy_hip.h).
 #pragma once
 #include <algorithm>
@@ -71,11 +77,28 @@ struct SpxRange {
 #define SPX_MAX_WALK_STREAMS 4
 #define SPX_RING (2 * SPX_MAX_WALK_STREAMS)
 // Pinned staging slot for the small host tables of a call (job tables, tile order): the async copies read it after the
-// call has returned, so it is plan-owned and reused only once its copies have retired.
+// call has returned, so it outlives the call (plan-owned, or a thread's own) and is reused only once its copies have retired.
+// The protocol, in this order: acquire, fill p, enqueue the reader, release on the reader's stream.  Under the owner's mutex.
 struct SpxStage {
   void* p = nullptr;
   size_t cap = 0;
   hipEvent_t done = nullptr;
+  int acquire(size_t bytes);      // a host wait for whatever last read the slot (or the event's creation), then room for `bytes`
+  int release(hipStream_t on);    // `done` recorded behind the reader
+  void destroy();
+};
+// Two slots taking turns: the reader of the slot a call takes was enqueued two calls ago, so acquire rarely has to wait.
+struct SpxStagePair {
+  SpxStage slot[2];
+  int next = 0;
+  SpxStage& take() { SpxStage& s = slot[next]; next ^= 1; return s; }
+  void destroy() { for (auto& s : slot) s.destroy(); }
+};
+// Workspace carving: consecutive parts, each on a 256-byte boundary (the base is rounded up too).
+struct SpxCarve {
+  size_t o;
+  explicit SpxCarve(size_t base = 0) : o((base + 255) & ~(size_t)255) {}
+  size_t take(size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; }
 };
 struct spx_plan {
   SpxPlanDev dev;
@@ -83,8 +106,7 @@ struct spx_plan {
   int cu_count = 1;
   size_t lds_per_cu = 65536;
   std::mutex mu;            // one launch sequence at a time per plan: side streams, events and staging are plan-owned
-  SpxStage stage[2];
-  int stage_next = 0;
+  SpxStagePair stage;
   // Mode trial for batch shapes where the register file admits only ONE analysis wave per SIMD beside the consumers:
   // whether the concurrent mode pays then depends on how long the walk is (16 kHz stereo: 3.4 ms concurrent, 3.8 in
   // sequence; 22.05 kHz mono: 3.0-4.6 against 2.3-3.2), so the second call of a shape runs concurrently and the third in
@@ -103,7 +125,6 @@ struct spx_plan {
   hipStream_t side = nullptr;
   hipStream_t side2 = nullptr;   // concurrent mode: the tension kernel's stream
   hipEvent_t ev_tension = nullptr;
-  hipEvent_t ev_start = nullptr;
   hipEvent_t ev_chunk[SPX_MAX_CHUNKS] = {};
   // spx_batch_run_ahead: the walk kernels of the plan's previous FOUR calls (ring_wait / ring_record below), the started-counter
   // of the last one
@@ -124,8 +145,8 @@ struct spx_plan {
   hipStream_t mix = nullptr;
   hipEvent_t ev_join = nullptr, ev_fork = nullptr, ev_an = nullptr;
   std::mutex mix_mu;
-  SpxStage mix_stage[2];         // (two, taking turns: a pipelined mixed call's upload sits behind the batch's H2D copy, and waiting
-  int mix_next = 0;              //  for the one slot's event made the host wait for that copy -- ADVICE r5)
+  SpxStagePair mix_stage;        // (two, taking turns: a pipelined mixed call's upload sits behind the batch's H2D copy, and waiting
+                                 //  for the one slot's event made the host wait for that copy -- ADVICE r5)
 };
 
 // ---- process-wide state (spx_engine.hip) ----
@@ -146,6 +167,28 @@ struct SpxDevGuard {
   bool valid = false;
 };
 extern SpxDevGuard g_guard[64];
+// A call's hold on its device's guard (run_impl, mixed_impl).  A call that wants the concurrent mode enters: the guard is locked
+// and the last concurrent call's event queried.  idle_start: that call (if any) has drained.  Still in flight on ANOTHER stream:
+// `redecide` runs with the guard locked, then the guard is unlocked (the call takes the sequential order).  Otherwise the guard
+// stays locked until the scope ends, by which time a concurrent call has left its own event behind (leave_event).
+struct SpxGuardScope {
+  SpxDevGuard& guard;
+  std::unique_lock<std::mutex> lock;
+  bool idle_start = false;
+  explicit SpxGuardScope(int device) : guard(g_guard[(device >= 0 && device < 64) ? device : 0]), lock(guard.mu, std::defer_lock) {}
+  template <class Redecide>
+  void enter(hipStream_t st, Redecide&& redecide) {
+    lock.lock();
+    const hipError_t q = guard.valid ? hipEventQuery(guard.last) : hipSuccess;
+    (void)hipGetLastError();  // hipErrorNotReady is not an error of this call
+    idle_start = (q == hipSuccess);
+    if (guard.valid && guard.last_stream != st && q == hipErrorNotReady) {
+      redecide();
+      lock.unlock();
+    }
+  }
+  int leave_event(hipStream_t st);   // this call's completion, for the next concurrent-mode call on the device (guard still locked)
+};
 
 // frame j is sent to the analysis once sample j*B + W has been written (soniclib.c:440-444)
 static inline int64_t frames_for(const SpxPlanDev& d, int64_t n_in) {
@@ -197,7 +240,21 @@ struct SpxRateCall {
   const int16_t* tsm_base = nullptr;                 // the base SpxRateJob::tsm_off counts from
   int max_blocks = 1;
 };
+// What every batch call is given (the arguments of spx_batch_run, in its order): the extern "C" entries fill one.
+struct SpxCall {
+  spx_plan_t plan;
+  const spx_stream_job* jobs;
+  int n;
+  const int16_t* in;
+  int16_t* out;
+  int64_t* n_out;
+  void* ws;
+  size_t ws_bytes;
+  const spx_taps* taps;
+  void* hs;
+};
 struct SpxCallOpts {
+  bool do_a = true, do_w = true;   // the analysis / the walk half of the call (spx_batch_analyze, spx_batch_walk: one of them)
   const SpxForce* force = nullptr;
   const SpxRateCall* rate = nullptr;   // spx_batch_run_rate with at least one rate != 1
   // spx_batch_run_map: DEVICE, the call's time map (spx_map_rows per job, in job order).  Handled like a rate call: the whole batch on
@@ -218,9 +275,30 @@ struct SpxCallOpts {
   void* done_event = nullptr;
   bool detached = false;
 };
-int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out, void* ws, size_t ws_bytes,
-             const spx_taps* taps, void* hs, bool do_a, bool do_w, const SpxCallOpts& opt = SpxCallOpts());
+int run_impl(const SpxCall& c, const SpxCallOpts& opt = SpxCallOpts());
+SpxModeRuntime mode_runtime(spx_plan* plan);   // zeroed, with the plan's device behind device_ours
+// the taps of a part of a call that begins `rows` frames in, with `spec` / `norm` elements of the two spectrum taps in front of it
+spx_taps taps_advance(const spx_taps& t, int64_t rows, int64_t spec, int64_t norm);
 // what a call refuses about its job table (spx_jobs.h, then the walk kernel's LDS window), asked before anything is enqueued
 SpxJobLimits spx_job_limits(spx_plan_t plan);
 int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call = false, bool short_window = false);
 int spx_read_steps(const SpxPlanDev& d, const spx_stream_job* jobs, int n, const void* ws, int32_t* steps, hipStream_t st);
+
+// ---- what the pipeline object (spx_pipeline.hip) calls ----
+void spx_internal_set_error(const char* msg);   // spx_plan.hip: other translation units' errors reach spx_last_error
+// spx_engine.hip: the call in its plain, pipelined (ahead) or overlapped order, behind in_ready, with done_event behind everything
+int spx_internal_run(const SpxCall& c, bool ahead, bool overlap, void* in_ready, void* done_event, bool detached);
+// ... and the rate call's side of a rate pipeline (spx_pipeline_create_rate)
+int spx_internal_rate_check(spx_plan_t plan, float rate);
+size_t spx_internal_rate_workspace_all(spx_plan_t plan, const spx_stream_job* jobs, int n);
+int spx_internal_run_rate(const SpxCall& c, const float* rates, void* in_ready, void* done_event);
+// spx_mixed.hip
+int spx_internal_run_mixed(const spx_plan_t* plans, int n_plans, const spx_stream_job* jobs, const int* plan_index, int n, const int16_t* in,
+                           int16_t* out, int64_t* n_out, void* ws, size_t ws_bytes, void* hs, bool ahead, void* in_ready,
+                           void* done_event, bool detached);
+// spx_convert.hip: the float batch call's conversion table and its two kernels, launched for a buffer set of the pipeline's
+size_t spx_conv_table_bytes(int n);
+int spx_conv_table_fill(void* pinned, const spx_stream_job* jobs, int n, int* max_in, int* max_out);
+void spx_conv_table_upload(const void* pinned, void* d_tab, int n, hipStream_t st);
+void spx_conv_launch_in(const void* d_tab, int n, int max_in, const float* in, int16_t* st_in, hipStream_t st);
+void spx_conv_launch_out(const void* d_tab, int n, int max_out, const int64_t* n_out, const int16_t* st_out, float* out, hipStream_t st);

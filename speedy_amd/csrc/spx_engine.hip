@@ -102,25 +102,53 @@ static bool device_is_ours(int dev) {
   return true;
 }
 
-extern "C" {
 
-}  // extern "C"
+// ---- the pinned staging slot's protocol (SpxStage, spx_engine.h) ----
+int SpxStage::acquire(size_t bytes) {
+  if (done) HIPCHK(hipEventSynchronize(done));  // whatever last read this slot has retired
+  else HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+  if (cap < bytes) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const size_t grown = bytes * 2 + 4096;
+    HIPCHK(hipHostMalloc(&p, grown, hipHostMallocDefault));
+    cap = grown;
+  }
+  return 0;
+}
+int SpxStage::release(hipStream_t on) {
+  HIPCHK(hipEventRecord(done, on));
+  return 0;
+}
+void SpxStage::destroy() {
+  if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+  if (p) (void)hipHostFree(p);
+  p = nullptr; cap = 0; done = nullptr;
+}
+int SpxGuardScope::leave_event(hipStream_t st) {
+  if (!guard.last) HIPCHK(hipEventCreateWithFlags(&guard.last, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(guard.last, st));
+  guard.last_stream = st;
+  guard.valid = true;
+  return 0;
+}
+
 Layout layout_for(const SpxPlanDev& d, const spx_stream_job* jobs, int n) {
   Layout L;
   int64_t tf = 0;
   for (int i = 0; i < n; i++) tf += (jobs[i].nonlinear != 0.0f) ? frames_for(d, jobs[i].n_in) : 0;
   L.total_frames = tf;
-  size_t o = 0;
-  L.off_streams = o; o += ((sizeof(SpxStreamDev) * (size_t)n * SPX_MAX_CHUNKS + 255) & ~(size_t)255);
-  L.off_states = o;  o += ((sizeof(SpxStreamState) * (size_t)n + 255) & ~(size_t)255);
-  L.off_rec = o;     o += ((sizeof(SpxFrameRec) * (size_t)(tf + 1) + 255) & ~(size_t)255);
-  L.off_scratch = o; o += ((sizeof(float) * 4 * (size_t)(tf + 1) + 255) & ~(size_t)255);
+  SpxCarve ws;
+  L.off_streams = ws.take(sizeof(SpxStreamDev) * (size_t)n * SPX_MAX_CHUNKS);
+  L.off_states = ws.take(sizeof(SpxStreamState) * (size_t)n);
+  L.off_rec = ws.take(sizeof(SpxFrameRec) * (size_t)(tf + 1));
+  L.off_scratch = ws.take(sizeof(float) * 4 * (size_t)(tf + 1));
   const int TFr = std::min(spx_analysis_small_tile_frames(), d.tile_frames > 0 ? d.tile_frames : spx_analysis_small_tile_frames());  // the smallest tile a call may take: an upper bound on tiles
   L.max_tiles = tf / TFr + n + 1;  // every stream may end with a partial tile
-  L.off_order = o;   o += ((sizeof(int) * (size_t)L.max_tiles + 255) & ~(size_t)255);
-  L.off_flags = o;   o += ((sizeof(int) * (size_t)L.max_tiles + 255) & ~(size_t)255);
-  L.off_ready = o;   o += ((sizeof(int) * ((size_t)n + 1) + 255) & ~(size_t)255);   // + the count of walk workgroups that have started
-  L.total = o;
+  L.off_order = ws.take(sizeof(int) * (size_t)L.max_tiles);
+  L.off_flags = ws.take(sizeof(int) * (size_t)L.max_tiles);
+  L.off_ready = ws.take(sizeof(int) * ((size_t)n + 1));   // + the count of walk workgroups that have started
+  L.total = ws.o;
   return L;
 }
 
@@ -206,8 +234,6 @@ spx_stage_kernel(const unsigned* __restrict__ src, unsigned* __restrict__ dst_a,
     }
   }
 }
-extern "C" {
-
 static hipEvent_t take_event() {
   std::lock_guard<std::mutex> g(g_tmu);
   if (!g_ev_free.empty()) { hipEvent_t e = g_ev_free.back(); g_ev_free.pop_back(); return e; }
@@ -215,8 +241,6 @@ static hipEvent_t take_event() {
   (void)hipEventCreate(&e);
   return e;
 }
-
-}  // extern "C"
 // The two side streams of the concurrent mode (analysis, tension) and of the time-chunk pipeline are per DEVICE, created once:
 // HIP maps streams onto a few hardware queues in creation order, and a queue runs its kernels in order -- with side streams
 // per plan, the second plan of a process got a tension stream that shared the caller stream's queue, its walk kernel waited
@@ -328,6 +352,33 @@ SpxModeEnv mode_env() {
   return e;
 }
 bool device_ours_cb(void* ctx) { return device_is_ours(*static_cast<int*>(ctx)); }
+SpxModeRuntime mode_runtime(spx_plan* plan) {
+  SpxModeRuntime T;
+  memset(&T, 0, sizeof(T));
+  T.device_ours = device_ours_cb;
+  T.device_ctx = &plan->device;
+  return T;
+}
+static SpxModeShape mode_shape(int n, int maxC, bool has_frames, const SpxCallOpts& opt) {
+  const SpxForce* force = opt.force;
+  SpxModeShape S;
+  S.n = n; S.max_channels = maxC; S.do_a = opt.do_a; S.do_w = opt.do_w; S.has_frames = has_frames;
+  S.forced = force != nullptr;
+  S.force_concurrent = force && force->concurrent != 0;
+  S.force_ahead = force && force->ahead_sa != nullptr;
+  S.force_total_streams = force ? force->total_streams : n;
+  S.ahead_req = opt.ahead_req; S.overlap_req = opt.overlap_req;
+  return S;
+}
+spx_taps taps_advance(const spx_taps& t, int64_t rows, int64_t spec, int64_t norm) {
+  spx_taps r = t;
+  if (r.tension) r.tension += rows;
+  if (r.speed) r.speed += rows;
+  if (r.features) r.features += rows * SPX_FEATURE_COUNT;
+  if (r.spectrogram) r.spectrogram += spec;
+  if (r.normalized) r.normalized += norm;
+  return r;
+}
 // What kind of speeds a batch's jobs bring: speedup_only -- every job speeds up (the walk kernel specialised for speeds >= 1
 // applies); any_speed -- not all do, but every speed is one the speed-up kernel's slow-down instantiations take (round 5).
 SpxSpeedClass speed_class(const spx_stream_job* jobs, int n) {
@@ -404,24 +455,15 @@ static int stage_tables(spx_plan* plan, const std::vector<SpxStreamDev>& sv, con
                         int* d_order, int* d_flags, unsigned n_flags, int* d_ready, unsigned n_ready, hipStream_t on, hipEvent_t* done,
                         const int* gate_started = nullptr, int gate_n = 0, unsigned gate_spins = 0) {
   const size_t b_sv = sizeof(SpxStreamDev) * sv.size(), b_or = sizeof(int) * order.size();
-  SpxStage& G = plan->stage[plan->stage_next];
-  plan->stage_next ^= 1;
-  if (G.done) HIPCHK(hipEventSynchronize(G.done));  // the kernel that last read this slot (two calls ago) has retired
-  else HIPCHK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
-  if (G.cap < b_sv + b_or) {
-    if (G.p) (void)hipHostFree(G.p);
-    G.p = nullptr; G.cap = 0;
-    const size_t cap = (b_sv + b_or) * 2 + 4096;
-    HIPCHK(hipHostMalloc(&G.p, cap, hipHostMallocDefault));
-    G.cap = cap;
-  }
+  SpxStage& G = plan->stage.take();
+  if (G.acquire(b_sv + b_or)) return -2;  // (a wait for the kernel that last read this slot, two calls ago)
   unsigned char* hp = static_cast<unsigned char*>(G.p);
   memcpy(hp, sv.data(), b_sv);
   if (b_or) memcpy(hp + b_sv, order.data(), b_or);
   hipLaunchKernelGGL(spx_stage_kernel, dim3(64), dim3(256), 0, on, reinterpret_cast<const unsigned*>(hp),
                      reinterpret_cast<unsigned*>(dstreams), (unsigned)(b_sv / 4), reinterpret_cast<unsigned*>(d_order), (unsigned)(b_or / 4),
                      reinterpret_cast<unsigned*>(d_flags), n_flags, reinterpret_cast<unsigned*>(d_ready), n_ready, gate_started, gate_n, gate_spins);
-  HIPCHK(hipEventRecord(G.done, on));
+  if (G.release(on)) return -2;
   *done = G.done;
   return 0;
 }
@@ -450,9 +492,9 @@ struct SpxTimed {
 //                   tiles of frames, then speeds, are handed over through flags the consumers poll;
 //   ahead        -- staging, analysis and tension kernels on the side stream AT ONCE, beside the previous call's walk kernel;
 //                   the walk kernel behind them on the caller's stream, or (walk2) on one of the library's walk streams.
-int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
-             int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs, bool do_a,
-             bool do_w, const SpxCallOpts& opt) {
+int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
+  const auto& [plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs] = call;
+  const bool do_a = opt.do_a, do_w = opt.do_w;
   const SpxForce* force = opt.force;
   // the choke point every call passes: a table that is refused has changed nothing of the plan and enqueued nothing
   // (general: the call runs on the general walk kernel whatever its speeds -- a rate call, a call with a time map)
@@ -483,22 +525,13 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   const SpxModeResources& R = mode_resources(plan, n, maxC, speedup_only, any_speed, short_window_res);
   hipStream_t st = static_cast<hipStream_t>(hs);
   // ---- decide ----
-  SpxModeShape S;
-  S.n = n; S.max_channels = maxC; S.do_a = do_a; S.do_w = do_w; S.has_frames = L.total_frames > 0;
-  S.forced = force != nullptr;
-  S.force_concurrent = force && force->concurrent != 0;
-  S.force_ahead = force && force->ahead_sa != nullptr;
-  S.force_total_streams = force ? force->total_streams : n;
-  S.ahead_req = opt.ahead_req; S.overlap_req = opt.overlap_req;
+  const SpxModeShape S = mode_shape(n, maxC, L.total_frames > 0, opt);
   SpxModeEnv E = mode_env();
   if (general) E.concurrent_enabled = false;   // a rate call's kernels run in sequence on the caller's stream (the rate kernel ends it); a map call's too
-  SpxModeRuntime T;
-  memset(&T, 0, sizeof(T));
+  SpxModeRuntime T = mode_runtime(plan);
   const int two_back = (plan->ahead_calls + SPX_RING - 2) % SPX_RING;
   T.two_workspaces = plan->ev_walk_valid[two_back] && plan->ring_ws[two_back] == ws;
   T.trial_key = ((long long)n << 40) ^ ((long long)L.total_frames << 8) ^ (maxC << 3) ^ (any_speed ? 4 : 0) ^ (speedup_only ? 2 : 0) ^ (opt.overlap_req ? 1 : 0);
-  T.device_ours = device_ours_cb;
-  T.device_ctx = &plan->device;
   spx_plan::Trial& TR = plan->trial;
   if (TR.state.key == T.trial_key && TR.state.choice < 0 && TR.state.calls >= 3 && TR.ev[1] && TR.ev[3] &&
       hipEventQuery(TR.ev[1]) == hipSuccess && hipEventQuery(TR.ev[3]) == hipSuccess)
@@ -508,20 +541,10 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   SpxMode M = spx_choose_mode(S, R, E, T, TR.state);
   // another concurrent-mode call still in flight on this device, on a different stream?  Then this one runs its kernels in
   // sequence (SpxDevGuard above); the guard stays locked until this call has left its own event behind.
-  SpxDevGuard& guard = g_guard[(plan->device >= 0 && plan->device < 64) ? plan->device : 0];
-  std::unique_lock<std::mutex> guard_lock(guard.mu, std::defer_lock);
-  bool idle_start = force ? force->idle_start : false;
-  if (M.want_concurrent && !force) {
-    guard_lock.lock();
-    const hipError_t q = guard.valid ? hipEventQuery(guard.last) : hipSuccess;
-    (void)hipGetLastError();  // hipErrorNotReady is not an error of this call
-    idle_start = (q == hipSuccess);   // the previous concurrent-mode call (if any) has drained
-    if (guard.valid && guard.last_stream != st && q == hipErrorNotReady) {
-      T.guard_busy = true;
-      M = spx_choose_mode(S, R, E, T, TR.state);
-      guard_lock.unlock();
-    }
-  }
+  SpxGuardScope guard(plan->device);
+  if (M.want_concurrent && !force)
+    guard.enter(st, [&] { T.guard_busy = true; M = spx_choose_mode(S, R, E, T, TR.state); });
+  const bool idle_start = force ? force->idle_start : guard.idle_start;
   static const bool dbg_trial = getenv("SPX_DEBUG_TRIAL") != nullptr;
   if (dbg_trial && TR.state.choice < 0 && M.trial_next.choice >= 0 && T.trial_times_ready)
     fprintf(stderr, "[spx trial] n=%d maxC=%d: concurrent %.3f ms, in sequence %.3f ms -> %s\n", n, maxC, T.ms_con, T.ms_seq,
@@ -582,7 +605,6 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
   if (nch > 1 || concurrent || ahead) {
     if (!plan->side) {
       if (dev_side_streams(plan->device, &plan->side, &plan->side2)) return fail(-1, "spx_batch: no side streams");
-      HIPCHK(hipEventCreateWithFlags(&plan->ev_start, hipEventDisableTiming));
       HIPCHK(hipEventCreateWithFlags(&plan->ev_tension, hipEventDisableTiming));
       for (auto& e : plan->ev_chunk) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
@@ -651,8 +673,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
     // producers queued behind a waiting consumer in a shared queue never start (every consumer is enqueued after its producers,
     // which is safe with any mapping).  So an idle start holds the analysis stream back with a gate kernel until the walk kernel's
     // workgroups have been placed (they count themselves in; spx_gate_kernel).
-    if (concurrent && do_w && idle_start)
-      hipLaunchKernelGGL(spx_gate_kernel, dim3(1), dim3(64), 0, sa, d_ready + n, n, 1200u);
+    if (concurrent && do_w && idle_start) spx_launch_gate(d_ready + n, n, 1200u, sa);
     if (do_a && tiles[c] > 0) {
       SpxTimed tm(timed, 0, sa);
       spx_launch_analysis(d, dj, n, tiles[c], in, rec, td, concurrent ? d_order : nullptr, concurrent ? d_flags : nullptr, maxC == 1, sa);
@@ -704,13 +725,7 @@ int run_impl(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* 
       HIPCHK(hipStreamWaitEvent(st, plan->ev_tension, 0));
     }
   }
-  if (concurrent && !force) {
-    // leave this call's completion behind for the next concurrent-mode call on the device (guard still locked)
-    if (!guard.last) HIPCHK(hipEventCreateWithFlags(&guard.last, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(guard.last, st));
-    guard.last_stream = st;
-    guard.valid = true;
-  }
+  if (concurrent && !force && guard.leave_event(st)) return -2;
   if (M.trial_slot >= 0) {
     hipEvent_t& e1 = TR.ev[2 * M.trial_slot + 1];
     if (!e1) HIPCHK(hipEventCreate(&e1));
@@ -743,20 +758,19 @@ static SplitPlan split_geometry(const spx_plan* plan, const spx_stream_job* jobs
   if (max_mult > SPX_SPLIT_LIMIT) max_mult = SPX_SPLIT_LIMIT;
   if (n <= cu || n > max_mult * cu) return P;
   P.k = (n + cu - 1) / cu;
-  size_t o = 0;
+  SpxCarve ws;
   for (int i = 0; i < P.k; i++) {
     const int a = (int)((long long)n * i / P.k), b = (int)((long long)n * (i + 1) / P.k);
     P.first.push_back(a);
     const size_t bytes = layout_for(plan->dev, jobs + a, b - a).total;
-    P.ws_off.push_back(o); P.ws_bytes.push_back(bytes);
-    o += (bytes + 255) & ~(size_t)255;
+    P.ws_off.push_back(ws.take(bytes)); P.ws_bytes.push_back(bytes);
   }
   P.first.push_back(n);
-  P.total = o;
+  P.total = ws.o;
   return P;
 }
-static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out, void* ws,
-                     size_t ws_bytes, const spx_taps* taps, void* hs, const SpxCallOpts& opt) {
+static int run_split(const SpxCall& call, const SpxCallOpts& opt) {
+  const auto& [plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs] = call;
   if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
   SplitPlan P = split_geometry(plan, jobs, n, opt.ahead_req && opt.overlap_req ? 2 : 1);
   if (P.k > 1 && (g_chunks_set.load() || ws_bytes < P.total)) P.k = 1;
@@ -767,20 +781,15 @@ static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
     std::lock_guard<std::mutex> plan_lock(plan->mu);
     const int m = P.first[1] - P.first[0];
     const SpxModeResources& R = mode_resources(plan, m, maxC, SC.speedup_only, SC.any_speed);
-    SpxModeShape S;
-    memset(&S, 0, sizeof(S));
-    S.n = m; S.max_channels = maxC; S.do_a = S.do_w = true; S.has_frames = true; S.force_total_streams = m;
-    S.ahead_req = S.overlap_req = true;
-    SpxModeRuntime T;
-    memset(&T, 0, sizeof(T));
+    SpxCallOpts overlapped;
+    overlapped.ahead_req = overlapped.overlap_req = true;
+    SpxModeRuntime T = mode_runtime(plan);
     T.trial_key = -2;
-    T.device_ours = device_ours_cb;
-    T.device_ctx = &plan->device;
     const SpxModeTrial none = {-1, 0, -1};
-    const SpxMode M = spx_choose_mode(S, R, mode_env(), T, none);
+    const SpxMode M = spx_choose_mode(mode_shape(m, maxC, true, overlapped), R, mode_env(), T, none);
     if (!(M.ahead && M.walk2)) P.k = 1;
   }
-  if (P.k <= 1) return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, opt);
+  if (P.k <= 1) return run_impl(call, opt);
   // every sub-batch's table before the first sub-batch is enqueued: a call that is refused has launched nothing
   for (int i = 0; i < P.k; i++)
     if (spx_check_jobs(plan, jobs + P.first[i], P.first[i + 1] - P.first[i])) return -1;
@@ -790,12 +799,7 @@ static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
     const int a = P.first[i], m = P.first[i + 1] - a;
     spx_taps t;
     if (taps) {
-      t = *taps;
-      if (t.tension) t.tension += rows;
-      if (t.speed) t.speed += rows;
-      if (t.features) t.features += rows * SPX_FEATURE_COUNT;
-      if (t.spectrogram) t.spectrogram += rows * (int64_t)plan->dev.N;
-      if (t.normalized) t.normalized += rows * (int64_t)plan->dev.W;
+      t = taps_advance(*taps, rows, rows * (int64_t)plan->dev.N, rows * (int64_t)plan->dev.W);
       for (int j = a; j < a + m; j++) rows += jobs[j].nonlinear != 0.0f ? frames_for(plan->dev, jobs[j].n_in) : 0;
     }
     SpxCallOpts o;
@@ -804,19 +808,17 @@ static int run_split(spx_plan_t plan, const spx_stream_job* jobs, int n, const i
     o.sub = i > 0;      // (the first sub-batch of an overlapped call is ordered like the call itself: "the same out buffer again")
     o.in_ready = opt.in_ready;
     if (i == P.k - 1) o.done_event = opt.done_event;   // (on hip_stream, which waits for every sub-batch's walk kernel: never detached)
-    const int rc = run_impl(plan, jobs + a, m, in, out, n_out + a, static_cast<unsigned char*>(ws) + P.ws_off[i], P.ws_bytes[i],
-                            taps ? &t : nullptr, hs, true, true, o);
+    const int rc = run_impl({plan, jobs + a, m, in, out, n_out + a, static_cast<unsigned char*>(ws) + P.ws_off[i], P.ws_bytes[i],
+                             taps ? &t : nullptr, hs}, o);
     if (rc) return rc;   // (a HIP error; what the earlier sub-batches enqueued is already joined to hip_stream: ring_record)
   }
   return 0;
 }
 
-int spx_internal_run(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out, void* ws,
-                     size_t ws_bytes, const spx_taps* taps, void* hs, bool ahead, bool overlap, void* in_ready, void* done_event,
-                     bool detached) {
+int spx_internal_run(const SpxCall& c, bool ahead, bool overlap, void* in_ready, void* done_event, bool detached) {
   SpxCallOpts o;
   o.ahead_req = ahead; o.overlap_req = overlap; o.in_ready = in_ready; o.done_event = done_event; o.detached = detached;
-  return run_split(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, o);
+  return run_split(c, o);
 }
 
 // What every batch call asks FIRST about its job table: the rules of spx_jobs.h for every job, then the one rule that needs a
@@ -847,27 +849,31 @@ size_t spx_batch_workspace_bytes(spx_plan_t plan, const spx_stream_job* jobs, in
 }
 int spx_batch_run(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
                   int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
-  return run_split(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, SpxCallOpts());
+  return run_split({plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs}, SpxCallOpts());
 }
 int spx_batch_run_ahead(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
                         int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
-  return spx_internal_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, false, nullptr, nullptr, false);
+  return spx_internal_run({plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs}, true, false, nullptr, nullptr, false);
 }
 int spx_batch_run_overlapped(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
                              int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
-  return spx_internal_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, nullptr, nullptr, false);
+  return spx_internal_run({plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs}, true, true, nullptr, nullptr, false);
 }
 int spx_batch_run_ahead_when(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
                              int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs, void* in_ready_event) {
-  return spx_internal_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, false, in_ready_event, nullptr, false);
+  return spx_internal_run({plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs}, true, false, in_ready_event, nullptr, false);
 }
 int spx_batch_analyze(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, void* ws,
                       size_t ws_bytes, const spx_taps* taps, void* hs) {
-  return run_impl(plan, jobs, n, in, nullptr, nullptr, ws, ws_bytes, taps, hs, true, false);
+  SpxCallOpts o;
+  o.do_w = false;
+  return run_impl({plan, jobs, n, in, nullptr, nullptr, ws, ws_bytes, taps, hs}, o);
 }
 int spx_batch_walk(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out,
                    int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
-  return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, false, true);
+  SpxCallOpts o;
+  o.do_a = false;
+  return run_impl({plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs}, o);
 }
 
 }  // extern "C"
@@ -895,10 +901,10 @@ static int64_t rate_frames(int64_t m, int old_rate, int new_rate) {
 // rates == nullptr: EVERY job gets its TSM buffer -- what a rate pipeline reserves, whose lanes may all resample in some batch.
 struct RateLayout { size_t off_table, off_tsm_n, off_tsm, total; std::vector<int64_t> tsm_off, tsm_cap; };
 static void rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, RateLayout& RL) {
-  size_t o = (spx_batch_workspace_bytes(plan, jobs, n) + 255) & ~(size_t)255;
-  RL.off_table = o; o += (sizeof(SpxRateJob) * (size_t)n + 255) & ~(size_t)255;
-  RL.off_tsm_n = o; o += (sizeof(int64_t) * (size_t)n + 255) & ~(size_t)255;
-  RL.off_tsm = o;
+  SpxCarve ws(spx_batch_workspace_bytes(plan, jobs, n));
+  RL.off_table = ws.take(sizeof(SpxRateJob) * (size_t)n);
+  RL.off_tsm_n = ws.take(sizeof(int64_t) * (size_t)n);
+  RL.off_tsm = ws.o;
   RL.tsm_off.assign(n, 0); RL.tsm_cap.assign(n, 0);
   int64_t v = 0;
   for (int i = 0; i < n; i++) {
@@ -907,14 +913,14 @@ static void rate_layout(spx_plan_t plan, const spx_stream_job* jobs, const float
     RL.tsm_cap[i] = spx_internal_out_bound(plan->dev, jobs[i].n_in, jobs[i].speed, jobs[i].nonlinear != 0.0f);
     v += (RL.tsm_cap[i] * jobs[i].channels + 7) & ~(int64_t)7;   // (every stream's buffer starts on a 16-byte boundary)
   }
-  RL.total = o + sizeof(int16_t) * (size_t)v + 128;
+  RL.total = ws.o + sizeof(int16_t) * (size_t)v + 128;   // (the last part: not rounded)
 }
 // What a call with rates hands run_impl (SpxCallOpts::rate): the rates judged, the workspace laid out, the SpxRateJob records and where
 // the walk kernel writes.  ONE builder for the batch call (spx_batch_run_rate) and the pipeline object's rate batches
 // (spx_internal_run_rate).  0 with *any = "a rate other than 1 is there" (false: RC is untouched, the call is spx_batch_run's), or
 // -1 with spx_last_error and nothing enqueued.
-static int rate_call_build(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
-                           const int64_t* n_out, void* ws, size_t ws_bytes, SpxRateCall& RC, bool* any_out) {
+static int rate_call_build(const SpxCall& call, const float* rates, SpxRateCall& RC, bool* any_out) {
+  const auto& [plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs] = call;
   bool any = false;
   std::vector<int> oldR(n, 1), newR(n, 1);
   if (rates)
@@ -983,18 +989,17 @@ size_t spx_internal_rate_workspace_all(spx_plan_t plan, const spx_stream_job* jo
 // Streams: the call uses hs alone (the side stream only for a call of more than two streams per CU, whose chunks it orders with
 // its own events), and on a pipeline whose calls are not detached hs already waits for every earlier walk kernel (ring_record);
 // on a detached pipeline it runs beside them, on other buffers.
-int spx_internal_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
-                          int64_t* n_out, void* ws, size_t ws_bytes, void* hs, void* in_ready, void* done_event) {
-  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+int spx_internal_run_rate(const SpxCall& c, const float* rates, void* in_ready, void* done_event) {
+  if (!c.plan || !c.jobs || c.n <= 0) return fail(-1, "spx_batch: bad arguments");
   SpxRateCall RC;
   bool any = false;
-  if (rate_call_build(plan, jobs, rates, n, in, out, n_out, ws, ws_bytes, RC, &any)) return -1;
+  if (rate_call_build(c, rates, RC, &any)) return -1;
   if (!any) return fail(-1, "spx_pipeline: internal: a batch of ones is not a rate call");
   SpxCallOpts o;
   o.rate = &RC;
   o.in_ready = in_ready;
   o.done_event = done_event;
-  return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, nullptr, hs, true, true, o);
+  return run_impl(c, o);   // (the pipeline's record has no taps)
 }
 extern "C" {
 int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, float nonlinear, float rate) {
@@ -1021,13 +1026,14 @@ size_t spx_batch_workspace_bytes_rate(spx_plan_t plan, const spx_stream_job* job
 int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
                        int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
   if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+  const SpxCall c = {plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs};
   SpxRateCall RC;
   bool any = false;
-  if (rate_call_build(plan, jobs, rates, n, in, out, n_out, ws, ws_bytes, RC, &any)) return -1;
-  if (!any) return spx_batch_run(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs);
+  if (rate_call_build(c, rates, RC, &any)) return -1;
+  if (!any) return run_split(c, SpxCallOpts());   // spx_batch_run
   SpxCallOpts o;
   o.rate = &RC;
-  return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, o);
+  return run_impl(c, o);
 }
 }  // extern "C"
 // Pitch searches per stream of the batch's last run (SpxWalkState::steps): the length of every stream's dependent chain.

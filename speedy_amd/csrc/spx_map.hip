@@ -73,25 +73,6 @@ spx_map_lookup_kernel(const SpxMapStream* __restrict__ streams, int stream0, int
   }
 }
 
-// One of the plan's two pinned staging slots (spx_engine.hip stage_tables has the protocol: a slot is rewritten only after a host
-// wait for the kernel that last read it), filled with `bytes` from `src`.  Under the plan's mutex.
-static int map_stage(spx_plan* plan, const void* src, size_t bytes, SpxStage** slot) {
-  SpxStage& G = plan->stage[plan->stage_next];
-  plan->stage_next ^= 1;
-  if (G.done) HIPCHK(hipEventSynchronize(G.done));
-  else HIPCHK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
-  if (G.cap < bytes) {
-    if (G.p) (void)hipHostFree(G.p);
-    G.p = nullptr; G.cap = 0;
-    const size_t cap = bytes * 2 + 4096;
-    HIPCHK(hipHostMalloc(&G.p, cap, hipHostMallocDefault));
-    G.cap = cap;
-  }
-  memcpy(G.p, src, bytes);
-  *slot = &G;
-  return 0;
-}
-
 extern "C" {
 
 int64_t spx_plan_map_rows(spx_plan_t plan, int64_t n_in, float nonlinear) {
@@ -110,7 +91,7 @@ int spx_batch_run_map(spx_plan_t plan, const spx_stream_job* jobs, int n, const 
   if (rows > 0x7fffffff) return fail(-1, "spx_batch_run_map: more than 2^31 - 1 map rows in one call");
   SpxCallOpts o;
   o.map = map;
-  return run_impl(plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs, true, true, o);
+  return run_impl({plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs}, o);
 }
 
 int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n, const int64_t* map, const int64_t* q_off, const int64_t* q,
@@ -129,8 +110,10 @@ int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n, const int
   }
   hipStream_t st = static_cast<hipStream_t>(hs);
   std::lock_guard<std::mutex> plan_lock(plan->mu);
-  SpxStage* G = nullptr;
-  if (map_stage(plan, tab.data(), sizeof(SpxMapStream) * (size_t)n, &G)) return -2;
+  // the table: through one of the plan's two pinned staging slots (SpxStage, spx_engine.h)
+  SpxStage& G = plan->stage.take();
+  if (G.acquire(sizeof(SpxMapStream) * (size_t)n)) return -2;
+  memcpy(G.p, tab.data(), sizeof(SpxMapStream) * (size_t)n);
   // query blocks per stream: the counts are the device's to know -- enough blocks to fill the device for a few streams, a
   // handful for many (a thread strides over what is left)
   int gx = 4096 / n;
@@ -138,9 +121,9 @@ int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n, const int
   for (int s0 = 0; s0 < n; s0 += 65535) {   // (the grid's second dimension holds 65 535)
     const int m = n - s0 < 65535 ? n - s0 : 65535;
     hipLaunchKernelGGL(spx_map_lookup_kernel, dim3((unsigned)gx, (unsigned)m), dim3(SPX_MAP_THREADS), 0, st,
-                       static_cast<const SpxMapStream*>(G->p), s0, B, map, q_off, q, r, inverse);
+                       static_cast<const SpxMapStream*>(G.p), s0, B, map, q_off, q, r, inverse);
   }
-  HIPCHK(hipEventRecord(G->done, st));
+  if (G.release(st)) return -2;
   HIPCHK(hipGetLastError());
   return 0;
 }

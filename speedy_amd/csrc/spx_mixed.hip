@@ -18,15 +18,14 @@ __global__ void spx_scatter_nout_kernel(const int64_t* __restrict__ src, const i
 struct MixedLayout { std::vector<size_t> ws_off, ws_bytes; size_t off_nout, off_idx, total; };
 static MixedLayout mixed_layout(const spx_plan_t* plans, int n_plans, const std::vector<std::vector<spx_stream_job>>& gj, int n) {
   MixedLayout M;
-  size_t o = 0;
+  SpxCarve ws;
   for (int g = 0; g < n_plans; g++) {
     const size_t b = gj[g].empty() ? 0 : layout_for(plans[g]->dev, gj[g].data(), (int)gj[g].size()).total;
-    M.ws_off.push_back(o); M.ws_bytes.push_back(b);
-    o += (b + 255) & ~(size_t)255;
+    M.ws_off.push_back(ws.take(b)); M.ws_bytes.push_back(b);
   }
-  M.off_nout = o; o += ((sizeof(int64_t) * (size_t)n + 255) & ~(size_t)255);
-  M.off_idx = o;  o += ((sizeof(int) * (size_t)n + 255) & ~(size_t)255);
-  M.total = o;
+  M.off_nout = ws.take(sizeof(int64_t) * (size_t)n);
+  M.off_idx = ws.take(sizeof(int) * (size_t)n);
+  M.total = ws.o;
   return M;
 }
 static int mixed_groups(int n_plans, const spx_stream_job* jobs, const int* plan_index, int n,
@@ -110,29 +109,16 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     G.push_back(mg);
   }
   const int groups = (int)G.size();
-  SpxModeRuntime T;
-  memset(&T, 0, sizeof(T));
-  T.device_ours = device_ours_cb;
-  T.device_ctx = &lead->device;
+  SpxModeRuntime T = mode_runtime(lead);
   const SpxModeEnv E = mode_env();
-  SpxMixedMode MM = spx_choose_mixed_mode(G.data(), groups, n, lead->cu_count, lead->lds_per_cu, spx_tension_lds_bytes(), spx_tension_vgprs(),
-                                          E, ahead_req, T);
+  auto choose = [&] {
+    return spx_choose_mixed_mode(G.data(), groups, n, lead->cu_count, lead->lds_per_cu, spx_tension_lds_bytes(), spx_tension_vgprs(), E, ahead_req, T);
+  };
+  SpxMixedMode MM = choose();
   // ---- the device guard, once for the whole call ----
-  SpxDevGuard& guard = g_guard[(lead->device >= 0 && lead->device < 64) ? lead->device : 0];
-  std::unique_lock<std::mutex> guard_lock(guard.mu, std::defer_lock);
-  SpxForce force = {0, false, n, nullptr, nullptr, nullptr, false};
-  if (MM.concurrent) {
-    guard_lock.lock();
-    const hipError_t q = guard.valid ? hipEventQuery(guard.last) : hipSuccess;
-    (void)hipGetLastError();
-    force.idle_start = (q == hipSuccess);
-    if (guard.valid && guard.last_stream != st && q == hipErrorNotReady) {
-      T.guard_busy = true;
-      MM = spx_choose_mixed_mode(G.data(), groups, n, lead->cu_count, lead->lds_per_cu, spx_tension_lds_bytes(), spx_tension_vgprs(), E,
-                                 ahead_req, T);
-      guard_lock.unlock();
-    }
-  }
+  SpxGuardScope guard(lead->device);
+  if (MM.concurrent) guard.enter(st, [&] { T.guard_busy = true; MM = choose(); });
+  SpxForce force = {0, guard.idle_start, n, nullptr, nullptr, nullptr, false};
   const bool concurrent = MM.concurrent;
   // pipelined with the previous call (spx_batch_run_mixed_ahead): kernels in sequence, one stream per CU at most
   const bool ahead = MM.ahead;
@@ -169,20 +155,11 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
   // (copied by the caller's stream -- or, pipelined, by the producers' stream below: the copy and its dispatch then are not part of
   // what the caller's stream runs between the previous call's walk kernel and this call's, 44 -> 25 us between the two)
   auto upload_idx = [&](hipStream_t on) -> int {
-    SpxStage& G = lead->mix_stage[lead->mix_next];
-    lead->mix_next ^= 1;
-    if (G.done) HIPCHK(hipEventSynchronize(G.done));
-    else HIPCHK(hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
-    if (G.cap < sizeof(int) * (size_t)n) {
-      if (G.p) (void)hipHostFree(G.p);
-      G.p = nullptr; G.cap = 0;
-      HIPCHK(hipHostMalloc(&G.p, sizeof(int) * (size_t)n * 2 + 1024, hipHostMallocDefault));
-      G.cap = sizeof(int) * (size_t)n * 2 + 1024;
-    }
+    SpxStage& G = lead->mix_stage.take();
+    if (G.acquire(sizeof(int) * (size_t)n)) return -2;
     memcpy(G.p, order.data(), sizeof(int) * (size_t)n);
     HIPCHK(hipMemcpyAsync(d_idx, G.p, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, on));
-    HIPCHK(hipEventRecord(G.done, on));
-    return 0;
+    return G.release(on);
   };
   if (!ahead && upload_idx(st)) return -2;
   std::vector<size_t> gpos(n_plans, 0);
@@ -193,12 +170,7 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
   if (taps) {
     size_t rows = 0, o_spec = 0, o_norm = 0;
     for (int g = 0; g < n_plans; g++) {
-      spx_taps& t = gtaps[g];
-      t.tension = taps->tension ? taps->tension + rows : nullptr;
-      t.speed = taps->speed ? taps->speed + rows : nullptr;
-      t.features = taps->features ? taps->features + rows * SPX_FEATURE_COUNT : nullptr;
-      t.spectrogram = taps->spectrogram ? taps->spectrogram + o_spec : nullptr;
-      t.normalized = taps->normalized ? taps->normalized + o_norm : nullptr;
+      gtaps[g] = taps_advance(*taps, (int64_t)rows, (int64_t)o_spec, (int64_t)o_norm);
       const size_t fr = gj[g].empty() ? 0 : (size_t)layout_for(plans[g]->dev, gj[g].data(), (int)gj[g].size()).total_frames;
       rows += fr; o_spec += fr * (size_t)plans[g]->dev.N; o_norm += fr * (size_t)plans[g]->dev.W;
     }
@@ -270,8 +242,7 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
     }
     SpxCallOpts go;
     go.force = &f;
-    rc = run_impl(p, gj[g].data(), (int)gj[g].size(), in, out, d_nout + gpos[g], w + M.ws_off[g], M.ws_bytes[g], taps ? &gtaps[g] : nullptr, gs,
-                  true, true, go);
+    rc = run_impl({p, gj[g].data(), (int)gj[g].size(), in, out, d_nout + gpos[g], w + M.ws_off[g], M.ws_bytes[g], taps ? &gtaps[g] : nullptr, gs}, go);
     // (also when the group failed -- a HIP error: its table passed spx_check_jobs above --: whatever it and the groups before it
     // enqueued on their streams still reads the caller's buffers, so the caller's stream waits for it before the error is returned)
     const std::string err = rc ? g_spx_err : std::string();
@@ -297,12 +268,7 @@ static int mixed_impl(const spx_plan_t* plans, int n_plans, const spx_stream_job
       for (int g = 0; g < n_plans; g++)
         if (started[g]) lead->mixed_started.emplace_back(started[g], (int)gj[g].size());
   }
-  if (concurrent) {
-    if (!guard.last) HIPCHK(hipEventCreateWithFlags(&guard.last, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(guard.last, st));
-    guard.last_stream = st;
-    guard.valid = true;
-  }
+  if (concurrent && guard.leave_event(st)) return -2;
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -53,33 +53,7 @@
 //                 spx_rate_batch_kernel into the slot's d_out  ->  offsets + gather (or the float conversion)  ->  record(done)
 // Never detached; no stream is added.  DESIGN.md "The rate pipeline" says where the order against neighbouring overlapped calls
 // comes from.
-#include <string.h>
-
-#include <string>
-#include <vector>
-
-#include "../../include/speedy_hip.h"
-#include "spx_internal.h"
-#include "spx_jobs.h"
-
-SpxJobLimits spx_job_limits(spx_plan_t plan);   // spx_engine.hip
-int spx_internal_run(spx_plan_t plan, const spx_stream_job* jobs, int n, const int16_t* in, int16_t* out, int64_t* n_out, void* ws,
-                     size_t ws_bytes, const spx_taps* taps, void* hs, bool ahead, bool overlap, void* in_ready, void* done_event, bool detached);
-int spx_internal_run_mixed(const spx_plan_t* plans, int n_plans, const spx_stream_job* jobs, const int* plan_index, int n, const int16_t* in,
-                           int16_t* out, int64_t* n_out, void* ws, size_t ws_bytes, void* hs, bool ahead, void* in_ready,
-                           void* done_event, bool detached);
-void spx_internal_set_error(const char* msg);
-// spx_engine.hip: the rate call's side of a rate pipeline (spx_pipeline_create_rate)
-int spx_internal_rate_check(spx_plan_t plan, float rate);
-size_t spx_internal_rate_workspace_all(spx_plan_t plan, const spx_stream_job* jobs, int n);
-int spx_internal_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
-                          int64_t* n_out, void* ws, size_t ws_bytes, void* hs, void* in_ready, void* done_event);
-// spx_convert.hip: the float batch call's conversion table and its two kernels, launched for a buffer set of the pipeline's
-size_t spx_conv_table_bytes(int n);
-int spx_conv_table_fill(void* pinned, const spx_stream_job* jobs, int n, int* max_in, int* max_out);
-void spx_conv_table_upload(const void* pinned, void* d_tab, int n, hipStream_t st);
-void spx_conv_launch_in(const void* d_tab, int n, int max_in, const float* in, int16_t* st_in, hipStream_t st);
-void spx_conv_launch_out(const void* d_tab, int n, int max_out, const int64_t* n_out, const int16_t* st_out, float* out, hipStream_t st);
+#include "spx_engine.h"   // the engine's entries this file calls ("what the pipeline object calls")
 
 #define SPX_PIPE_MAX_DEPTH 8
 #define PIPE_ALIGN 32   // int16 values: every stream's region starts at a 64-byte boundary, in device and in host memory
@@ -501,18 +475,18 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, con
   // cannot be detached from it and takes the order the host-output pipeline takes)
   bool event_recorded = false;
   const bool detach = !host_out && !flt;
+  const SpxCall call = {p->plans[0], S.jobs.data(), p->n, dev_in, S.d_out, S.d_nout, S.ws, p->ws_bytes, nullptr, p->s_run};
   if (resample) {
     // (never detached: the rate kernel ends the call on the run stream, where the slot's event is recorded below.  The rates are read
     // before the call returns: they reach the device inside the SpxRateJob records, through the engine's staging kernel)
-    rc = spx_internal_run_rate(p->plans[0], S.jobs.data(), rates, p->n, dev_in, S.d_out, S.d_nout, S.ws, p->ws_bytes, p->s_run, in_ready, nullptr);
+    rc = spx_internal_run_rate(call, rates, in_ready, nullptr);
   } else if (p->mixed) {
     // (round 6: detached like a one-plan batch -- the groups' walk kernels on the library's walk streams, two calls' worth in flight)
     rc = spx_internal_run_mixed(p->plans.data(), (int)p->plans.size(), S.jobs.data(), p->plan_index.data(), p->n, dev_in, S.d_out, S.d_nout,
                                 S.ws, p->ws_bytes, p->s_run, true, in_ready, detach ? S.ev_done : nullptr, detach);
     event_recorded = detach;
   } else {
-    rc = spx_internal_run(p->plans[0], S.jobs.data(), p->n, dev_in, S.d_out, S.d_nout, S.ws, p->ws_bytes, nullptr, p->s_run, true, true, in_ready,
-                          detach ? S.ev_done : nullptr, detach);
+    rc = spx_internal_run(call, true, true, in_ready, detach ? S.ev_done : nullptr, detach);
     event_recorded = detach;
   }
   if (rc) {

@@ -261,20 +261,13 @@ void spx_plan_destroy(spx_plan_t plan) {
   if (plan->ev_join) (void)hipEventDestroy(plan->ev_join);
   if (plan->ev_an) (void)hipEventDestroy(plan->ev_an);
   if (plan->ev_fork) (void)hipEventDestroy(plan->ev_fork);
-  for (auto& g : plan->mix_stage) {
-    if (g.done) { (void)hipEventSynchronize(g.done); (void)hipEventDestroy(g.done); }
-    if (g.p) (void)hipHostFree(g.p);
-  }
+  plan->mix_stage.destroy();
   if (plan->ev_tension) (void)hipEventDestroy(plan->ev_tension);
-  if (plan->ev_start) (void)hipEventDestroy(plan->ev_start);
   for (auto& e : plan->ev_chunk) if (e) (void)hipEventDestroy(e);
   for (auto& e : plan->trial.ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : plan->ev_walk) if (e) { (void)hipEventSynchronize(e); (void)hipEventDestroy(e); }
   for (auto& e : plan->ev_call) if (e) (void)hipEventDestroy(e);
-  for (auto& g : plan->stage) {
-    if (g.done) { (void)hipEventSynchronize(g.done); (void)hipEventDestroy(g.done); }
-    if (g.p) (void)hipHostFree(g.p);
-  }
+  plan->stage.destroy();
   if (plan->tables) (void)hipFree(plan->tables);
   delete plan;
 }
