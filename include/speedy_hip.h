@@ -454,6 +454,14 @@ void spx_set_pipeline_chunks(int chunks);
  * internal HIP streams, the walk kernel at the same time on hip_stream; tiles of frames and then per-frame speeds are
  * handed over through device-scope flags as they become ready.  Results are identical with it on or off. */
 void spx_set_concurrent(int on);
+/* Which frame-rate (tension) kernel a batch call launches.  0 (default): a launch that hands over no tile flags -- kernels in
+ * sequence, pipelined and overlapped calls, time chunks, sub-batches -- takes spx_tension_seq_kernel (one pass over LDS, the three
+ * recurrences side by side), the concurrent mode spx_tension_kernel (it polls the tile flags).  1: spx_tension_kernel always.
+ * Results are identical bit for bit; the switch is for differential tests and for A/B runs of one library. */
+void spx_set_tension_form(int form);
+/* Diagnostics: the tension kernel the last batch call of this process launched, 0 = spx_tension_kernel, 1 = spx_tension_seq_kernel
+ * (the streaming and unit-level APIs always launch the former and leave this value alone). */
+int spx_debug_last_tension_form(void);
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls);
 /* "analysis;tension;walk": the kernels (template arguments included, as a profiler prints them) that serve a batch of
  * n_streams streams with at most max_channels channels; speedup_only = every job has speed > 1. */

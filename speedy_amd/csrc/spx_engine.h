@@ -154,6 +154,8 @@ struct EvPair { hipEvent_t a, b; int kind; };  // kind 0 = analysis launch, 1 = 
 extern std::atomic<bool> g_timing;
 extern std::atomic<int> g_last_concurrent;   // spx_debug_last_call_concurrent (2 = pipelined with the previous call)
 extern std::atomic<int> g_concurrent;        // spx_set_concurrent
+extern std::atomic<int> g_tension_form;      // spx_set_tension_form
+extern std::atomic<int> g_last_tension_form; // spx_debug_last_tension_form (run_impl alone sets it)
 extern std::atomic<bool> g_chunks_set;       // the caller chose a chunk count (spx_set_pipeline_chunks)
 extern std::atomic<int> g_chunks;
 extern std::mutex g_tmu;

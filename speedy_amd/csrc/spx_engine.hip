@@ -24,6 +24,8 @@ thread_local std::string g_spx_err;
 std::atomic<bool> g_timing{false};
 std::atomic<int> g_last_concurrent{0};   // spx_debug_last_call_concurrent (2 = pipelined with the previous call)
 std::atomic<int> g_concurrent{1};  // spx_set_concurrent: analysis and walk kernels on two streams, tile-flag hand-off
+std::atomic<int> g_tension_form{0};       // spx_set_tension_form: 1 = spx_tension_kernel for every launch
+std::atomic<int> g_last_tension_form{SPX_TENSION_POLL};   // spx_debug_last_tension_form
 std::atomic<bool> g_chunks_set{false};  // the caller chose a chunk count (spx_set_pipeline_chunks)
 std::atomic<int> g_chunks{1};  // spx_set_pipeline_chunks (measured on MI355X, 256 x 10 s: 1 -> 5.09 ms, 2 -> 5.25, 4 -> 5.54 per step)
 std::mutex g_tmu;
@@ -687,7 +689,9 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
       hipStream_t stn = concurrent ? plan->side2 : (ahead ? sa : st);
       {
         SpxTimed tm(timed, 2, stn);
-        spx_launch_tension(d, dj, n, states, rec, scratch, td, concurrent ? d_flags : nullptr, (concurrent || ahead) ? d_ready : nullptr, stn);
+        // no tile flags to poll: the one-pass kernel (spx_set_tension_form(1) keeps the polling kernel for A/B runs)
+        const int form = (!concurrent && g_tension_form.load(std::memory_order_relaxed) == 0) ? SPX_TENSION_SEQ : SPX_TENSION_POLL;
+        g_last_tension_form = spx_launch_tension(d, dj, n, states, rec, scratch, td, concurrent ? d_flags : nullptr, (concurrent || ahead) ? d_ready : nullptr, stn, form);
       }
       if (concurrent || ahead) HIPCHK(hipEventRecord(plan->ev_tension, stn));
       if (ahead) HIPCHK(hipStreamWaitEvent(stw, plan->ev_tension, 0));   // the walk kernel starts when every speed of the call is there

@@ -204,9 +204,20 @@ void spx_launch_analysis_frames(const SpxPlanDev& P, const SpxStreamDev* streams
                                 bool preemph, SpxFrameRec* rec, SpxTapsDev taps, hipStream_t st);
 // Frame-rate stage: energy / hysteresis / difference filters -> tension -> speed per tension frame (scratch[4k+3]) and
 // the tension, speed and feature taps.  tile_flags / speed_ready: the concurrent-mode hand-off (nullptr = sequential).
-void spx_launch_tension(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, SpxStreamState* states,
-                        const SpxFrameRec* rec, float* scratch, SpxTapsDev taps, const int* tile_flags, int* speed_ready,
-                        hipStream_t st);
+// form: which kernel -- SPX_TENSION_POLL spx_tension_kernel (four passes, polls tile flags where given: the concurrent mode's
+// consumer, and the kernel of the streaming and unit-level call sites), SPX_TENSION_SEQ spx_tension_seq_kernel (one pass over LDS,
+// the three recurrences side by side; launches without tile flags only -- asked for with flags, the polling kernel runs).  Both
+// write the same bits to the same places.  Returns the form launched.
+#define SPX_TENSION_POLL 0
+#define SPX_TENSION_SEQ 1
+int spx_launch_tension(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, SpxStreamState* states,
+                       const SpxFrameRec* rec, float* scratch, SpxTapsDev taps, const int* tile_flags, int* speed_ready,
+                       hipStream_t st, int form = SPX_TENSION_POLL);
+// spx_tension_seq.hip: the launch itself (called by spx_launch_tension alone) and whether the kernel's rings hold the plan's
+// hysteresis reach (F, Pp at most one block: every plan's are 8 and 12)
+void spx_launch_tension_seq(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, SpxStreamState* states,
+                            const SpxFrameRec* rec, float* scratch, SpxTapsDev taps, int* speed_ready, hipStream_t st);
+bool spx_tension_seq_serves(const SpxPlanDev& P);
 // An instantiation of a kernel template as its family's selector picked it (spx_analysis_select, spx_walk_select,
 // spx_walk_fast_select -- each the ONE place its template-ids are written): the launch, the register query and the kernel's
 // name (spx_batch_kernel_names) all come from the same pick.

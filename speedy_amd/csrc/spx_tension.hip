@@ -353,10 +353,18 @@ void spx_launch_speed_from_tension(SpxStreamState* state, float tension, float R
   hipLaunchKernelGGL(spx_speed_kernel, dim3(1), dim3(64), 0, st, state, tension, Rg, feedback, speed_out);
 }
 
-void spx_launch_tension(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, SpxStreamState* states,
-                        const SpxFrameRec* rec, float* scratch, SpxTapsDev taps, const int* tile_flags, int* speed_ready,
-                        hipStream_t st) {
-  if (n_streams <= 0) return;
+// The one place that launches a tension kernel.  SPX_TENSION_SEQ is honoured only without tile flags: spx_tension_seq_kernel
+// (spx_tension_seq.hip, a code object of its own) does not poll.  Returns the form it launched.
+int spx_launch_tension(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, SpxStreamState* states,
+                       const SpxFrameRec* rec, float* scratch, SpxTapsDev taps, const int* tile_flags, int* speed_ready,
+                       hipStream_t st, int form) {
+  if (form == SPX_TENSION_SEQ && (tile_flags != nullptr || !spx_tension_seq_serves(P))) form = SPX_TENSION_POLL;
+  if (n_streams <= 0) return form;
+  if (form == SPX_TENSION_SEQ) {
+    spx_launch_tension_seq(P, streams, n_streams, states, rec, scratch, taps, speed_ready, st);
+    return form;
+  }
   hipLaunchKernelGGL(spx_tension_kernel, dim3(n_streams), dim3(SPX_TENSION_THREADS), 0, st, P, streams, states, rec,
                      scratch, taps, tile_flags, speed_ready);
+  return form;
 }
