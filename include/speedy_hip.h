@@ -159,6 +159,62 @@ int spx_batch_run_map(spx_plan_t plan, const spx_stream_job* jobs, int n_streams
 int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int64_t* map, const int64_t* q_off,
                    const int64_t* q, int64_t* r, int inverse, void* hip_stream);
 
+/* ---- TWO PASSES IN ONE CALL: every stream to a target length, or the linear control at the nonlinear duration ----
+ * The reference's CLI has two two-pass drivers (speedy_wave.cc:424-462): --length runs a nonlinear pass at the requested speed,
+ * measures what came out and runs the final pass at want * (want / achieved), so that the output lands on the requested duration;
+ * --match_nonlinear runs the same measuring pass and then the final (normally linear) pass at exactly the achieved speed.
+ * spx_batch_run_twopass is both, per stream, for a whole batch -- asynchronous on hip_stream, with NO host wait and no
+ * device-to-host copy between the passes: the second-pass speeds are worked out on the device.
+ *   seconds  HOST double[n_streams] or NULL.  Per stream i, with T = jobs[i].n_in and rate = the plan's sample rate:
+ *     MATCH   seconds == NULL or seconds[i] == 0:   want = (double)jobs[i].speed
+ *     LENGTH  seconds[i] > 0:   want = (double)((float)T / (float)rate) / seconds[i]   (jobs[i].speed is ignored)
+ *   probe pass   the job with speed (float)want, nonlinear 1 and the job's feedback; its count goes to n_probe[i]
+ *   achieved     got = (double)T / (double)n_probe[i]
+ *   speeds[i]    MATCH (float)got;  LENGTH (float)(want * (want / got));  n_probe[i] <= 0 (an empty stream, one too short to emit
+ *                anything, out_cap too small for the probe, a lost producer): (float)want.  IEEE double arithmetic, each operation
+ *                rounded once; the types and rounding points of tools/speedy_wave_hip.cpp:179-191.
+ *   final pass   the job as given, at speed speeds[i]
+ *   n_probe, speeds   DEVICE int64[n_streams], float[n_streams]: written by the call, for the caller to read behind it
+ * out, n_out and the taps are byte for byte what spx_batch_run gives the final table (the jobs with speeds[i] as their speed): a
+ * negative n_out where out_cap is too small, nothing written past out_off + out_cap * channels.  The probe pass's audio passes
+ * through the same out region first (at most out_cap frames of it); values of the region behind the final count are unspecified.
+ * Refused with -1 and spx_last_error, nothing enqueued, the plan as it was: whatever spx_batch_run refuses in the probe table or in
+ * the final table; a NULL n_probe or speeds; a seconds[i] that is negative or not finite; a want whose float value is not finite and
+ * > 0 (LENGTH on an empty stream is one); a stream with want * want * (out_cap + 1) >= 1e18 -- the bound that keeps every speed the
+ * device can compute inside the range the walk kernels serve; a workspace smaller than spx_batch_workspace_bytes_twopass (the probe
+ * table's spx_batch_workspace_bytes and the retarget table behind it; 0 with spx_last_error for a table that is refused).
+ * CAPACITY: spx_plan_out_capacity_twopass(n_in, want, nonlinear) is the larger of spx_plan_out_capacity_for(n_in, (float)want, 1)
+ * -- the probe -- and spx_plan_out_capacity_for(n_in, (float)want, nonlinear); -1 for values spx_batch_run refuses.  What that covers
+ * of the final pass, whose speed is not known beforehand:
+ *   want >= 1   n_in + slack: a second-pass speed >= 1, nonlinear or linear.  MATCH stays there (a nonlinear probe at a speed >= 1
+ *               never emits more than it consumes, so got >= 1 up to the flush padding of a stream of a few hundred frames); LENGTH
+ *               leaves it when got > want * want, that is when the probe overshot a want close to 1 by more than want itself.
+ *   want < 1    (n_in + flush padding) * 200 + slack: every second-pass speed of a nonlinear job, and of a linear job down to 0.01.
+ * Outside of that the final count may come back negative -- never a write past the region.
+ * COST: where every final job is nonlinear the second pass runs WITHOUT an analysis launch, on the frame records the first pass
+ * left in the workspace (spx_debug_last_twopass bit 0) -- the analysis does not depend on the speed; a batch with a linear final job
+ * runs the second pass's analysis for whatever is nonlinear.  The second pass's kernels run in sequence on hip_stream, and its walk
+ * kernel is the any-speed instantiation (the speed class cannot be read off a speed the host does not know).  Measured, 256 x 10 s,
+ * 16 kHz mono, LENGTH at 3.5x, call after call (profiles/twopass.txt): this call 4.03 ms; the loop a caller writes without it --
+ * spx_batch_run, the counts to the host, the formula, spx_batch_run -- 3.55 ms; one spx_batch_run 1.72 ms.  So for such a batch the
+ * call is 0.48 ms SLOWER than the loop: both of the loop's calls run their three kernels side by side on the speed-up-only walk
+ * kernel, where the analysis hides beside the walk kernel (saving its launch saves nothing a step waits for), and the loop's idle gap
+ * is only about 0.1 ms.  The second pass here takes 2.31 ms, and a kernel trace says where: retarget kernel 5 us, tension kernel
+ * 33 us, no gap between the passes, and a walk kernel of 2.19 ms in its any-speed instantiation against 1.71 in the speed-up-only
+ * one -- the whole 0.48 ms.  What the call offers today is its shape -- one asynchronous call, no host wait between the passes -- not
+ * time; a speed class decided on the device (the speed-up-only kernel where every patched speed is above 1) is the follow-up.  Consecutive calls: the second pass's job table waits, on the host, for the staging kernel of the
+ * previous call's second pass (the plan's two pinned staging slots taking turns), that is until the previous call's first pass has
+ * finished -- the GPU still has the previous second pass to run by then.
+ * The plain call only.  OUT OF SCOPE: the _rate, _float, _map, _ahead / _overlapped and _mixed* forms, the pipeline object, a probe
+ * that writes no audio, more than one correction step. */
+size_t spx_batch_workspace_bytes_twopass(spx_plan_t plan, const spx_stream_job* jobs, const double* seconds, int n_streams);
+int64_t spx_plan_out_capacity_twopass(spx_plan_t plan, int64_t n_in, double want, float nonlinear);
+int spx_batch_run_twopass(spx_plan_t plan, const spx_stream_job* jobs, const double* seconds, int n_streams, const int16_t* in,
+                          int16_t* out, int64_t* n_out, int64_t* n_probe, float* speeds, void* workspace, size_t workspace_bytes,
+                          const spx_taps* taps, void* hip_stream);
+/* Diagnostics: bit 0 = the last two-pass call reused the first pass's analysis. */
+int spx_debug_last_twopass(void);
+
 /* spx_batch_run_rate on FLOAT samples in device memory (sonicWriteFloatToStream / sonicReadFloatFromStream, sonic2.h:64-68).
  *   in   DEVICE  float input samples in (-1, 1), 4-byte aligned; read once, exactly the jobs' values: no padding behind the end
  *   out  DEVICE  float output samples, 4-byte aligned (every value an int16 / 32767.0f, the IEEE quotient)

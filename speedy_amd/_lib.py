@@ -51,6 +51,11 @@ SYMBOLS = {
                                     C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
     "spx_map_lookup": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p]),
+    "spx_batch_workspace_bytes_twopass": (C.c_size_t, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int]),
+    "spx_plan_out_capacity_twopass": (C.c_int64, [C.c_void_p, C.c_int64, C.c_double, C.c_float]),
+    "spx_batch_run_twopass": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
+    "spx_debug_last_twopass": (C.c_int, []),
     "spx_batch_workspace_bytes_float": (C.c_size_t, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_int]),
     "spx_batch_run_float": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),

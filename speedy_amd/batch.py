@@ -78,8 +78,7 @@ class Batch:
         self.in_offs, self.out_offs, self.out_caps, self.frame_offs, self.frames = [], [], [], [], []
         fo = 0
         for i in range(n):
-            cap = plan.out_capacity(int(self.lengths[i]), float(sp[i]), float(nlv[i]),
-                                    None if self.rates is None else float(self.rates[i]))
+            cap = self._capacity(i, int(self.lengths[i]), float(sp[i]), float(nlv[i]))
             j = self.jobs[i]
             j.in_off, j.n_in, j.out_off, j.out_cap = in_off, int(self.lengths[i]), out_off, cap
             j.channels, j.speed, j.nonlinear, j.feedback = int(ch[i]), float(sp[i]), float(nlv[i]), float(fb[i])
@@ -98,13 +97,7 @@ class Batch:
         self.d_in = torch.zeros(max(1, in_off) + 64, dtype=torch.int16, device=dev)
         self.d_out = torch.zeros(max(1, out_off), dtype=torch.int16, device=dev)
         self.d_nout = torch.zeros(n, dtype=torch.int64, device=dev)
-        if self.rates is None:
-            wsb = plan.L.spx_batch_workspace_bytes(plan.h, self.jobs, n)
-        else:
-            wsb = plan.L.spx_batch_workspace_bytes_rate(plan.h, self.jobs, self._rates_ptr(), n)
-            if wsb == 0:
-                raise RuntimeError("spx_batch_workspace_bytes_rate: " + plan.L.spx_last_error().decode())
-        self.d_ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
+        self.d_ws = torch.zeros(self._workspace_bytes(), dtype=torch.uint8, device=dev)
         if self.with_map:
             # stream i's rows: d_map[map_offs[i] : map_offs[i + 1]] (spx_plan_map_rows per job, in job order)
             self.map_offs = [0]
@@ -124,6 +117,20 @@ class Batch:
                 self.t_norm = torch.zeros(T1 * plan.W, dtype=torch.float32, device=dev)
                 self.taps.spectrogram = self.t_spec.data_ptr()
                 self.taps.normalized = self.t_norm.data_ptr()
+
+    def _capacity(self, i, n_in, speed, nonlinear):
+        """Output capacity of stream i in frames (a subclass with another capacity rule overrides this)."""
+        return self.plan.out_capacity(n_in, speed, nonlinear, None if self.rates is None else float(self.rates[i]))
+
+    def _workspace_bytes(self):
+        """Device workspace of the call run() makes."""
+        plan = self.plan
+        if self.rates is None:
+            return plan.L.spx_batch_workspace_bytes(plan.h, self.jobs, self.n)
+        wsb = plan.L.spx_batch_workspace_bytes_rate(plan.h, self.jobs, self._rates_ptr(), self.n)
+        if wsb == 0:
+            raise RuntimeError("spx_batch_workspace_bytes_rate: " + plan.L.spx_last_error().decode())
+        return wsb
 
     def upload(self, streams):
         """streams: list of int16 numpy arrays (interleaved).  Packs and copies them to HBM."""
@@ -275,6 +282,73 @@ class Batch:
             r["spectrogram"] = self.t_spec[fo * N:(fo + T) * N].cpu().numpy().reshape(T, N)
             r["normalized"] = self.t_norm[fo * W:(fo + K) * W].cpu().numpy().reshape(K, W)
         return r
+
+
+class TwoPassBatch(Batch):
+    """Two passes in one call (spx_batch_run_twopass): every stream is probed with a fully nonlinear pass, and the final pass runs
+    at a speed the GPU works out from the probe's count -- nothing comes back to the host in between.
+    seconds: None or 0 for a stream = MATCH mode, the final pass runs the job (its `nonlinear`, normally 0: the linear control) at
+    the speed the nonlinear probe at `speed` achieved (speedy_wave --match_nonlinear); a value > 0 = LENGTH mode, the stream is
+    brought to that many seconds (speedy_wave --length) and `speed` is ignored.  One value or one per stream.
+    out_caps: output capacities in frames instead of spx_plan_out_capacity_twopass's.
+    results() as Batch's; probe_counts() and final_speeds() return what the call measured and decided.  The plain call only."""
+
+    def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
+                 spectrogram_taps=False, seconds=None, out_caps=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
+        n = len(lengths)
+        sec = np.zeros(n, np.float64) if seconds is None else np.broadcast_to(np.asarray(seconds, np.float64), (n,))
+        self.seconds = np.ascontiguousarray(sec, np.float64)
+        sp = np.broadcast_to(np.asarray(speed, np.float32), (n,))
+        # the speed each probe runs at, with the call's own types: (double)((float)T / (float)rate) / seconds, or the job's speed
+        self.want = np.array([np.float64(np.float32(int(lengths[i])) / np.float32(plan.sample_rate)) / self.seconds[i]
+                              if self.seconds[i] > 0 else np.float64(sp[i]) for i in range(n)], np.float64)
+        self._out_caps = None if out_caps is None else np.broadcast_to(np.asarray(out_caps, np.int64), (n,))
+        # (the table's speed: what MATCH mode reads; LENGTH mode ignores it)
+        super().__init__(plan, lengths, channels, self.want.astype(np.float32), nonlinear, feedback, device, taps, spectrogram_taps)
+        self.d_probe = torch.zeros(n, dtype=torch.int64, device=self.device)
+        self.d_speeds = torch.zeros(n, dtype=torch.float32, device=self.device)
+
+    def _seconds_ptr(self):
+        return self.seconds.ctypes.data_as(C.POINTER(C.c_double))
+
+    def _capacity(self, i, n_in, speed, nonlinear):
+        if self._out_caps is not None:
+            return int(self._out_caps[i])
+        cap = self.plan.L.spx_plan_out_capacity_twopass(self.plan.h, n_in, float(self.want[i]), nonlinear)
+        if cap < 0:
+            raise RuntimeError("spx_plan_out_capacity_twopass: " + self.plan.L.spx_last_error().decode())
+        return cap
+
+    def _workspace_bytes(self):
+        wsb = self.plan.L.spx_batch_workspace_bytes_twopass(self.plan.h, self.jobs, self._seconds_ptr(), self.n)
+        if wsb == 0:
+            raise RuntimeError("spx_batch_workspace_bytes_twopass: " + self.plan.L.spx_last_error().decode())
+        return wsb
+
+    def run(self, stream=None):
+        """Enqueue both passes and the retarget kernel between them on `stream` (torch stream or None)."""
+        hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        rc = self.plan.L.spx_batch_run_twopass(self.plan.h, self.jobs, self._seconds_ptr(), self.n, self.d_in.data_ptr(),
+                                               self.d_out.data_ptr(), self.d_nout.data_ptr(), self.d_probe.data_ptr(),
+                                               self.d_speeds.data_ptr(), self.d_ws.data_ptr(), self.d_ws.numel(),
+                                               C.byref(self.taps) if self.taps is not None else None, hs)
+        if rc != 0:
+            raise RuntimeError("spx_batch_run_twopass: " + self.plan.L.spx_last_error().decode())
+
+    def run_ahead(self, stream=None, in_ready=None, overlap=False):
+        raise RuntimeError("a two-pass batch runs through the plain call only (spx_batch_run_twopass)")
+
+    def probe_counts(self):
+        """Frames the probe pass produced per stream (host numpy int64; <= 0: nothing to measure); synchronises."""
+        torch.cuda.synchronize(self.device)
+        return self.d_probe.cpu().numpy().copy()
+
+    def final_speeds(self):
+        """The speed the final pass ran at per stream (host numpy float32); synchronises."""
+        torch.cuda.synchronize(self.device)
+        return self.d_speeds.cpu().numpy().copy()
 
 
 class FloatBatch(Batch):
@@ -756,6 +830,19 @@ def compress_batch_float(streams, sample_rate, channels, speed, nonlinear=1.0, f
     ch = np.broadcast_to(np.asarray(channels, np.int32), (len(streams),))
     lengths = [np.asarray(x).size // int(c) for x, c in zip(streams, ch)]
     b = FloatBatch(plan, lengths, channels, speed, nonlinear, feedback, taps=taps, spectrogram_taps=spectrogram_taps, rate=rate)
+    b.upload(streams)
+    b.run()
+    return b.results(), b
+
+
+def compress_batch_to_length(streams, sample_rate, channels, seconds, nonlinear=1.0, feedback=0.0, match_matlab=False,
+                             taps=False, spectrogram_taps=False):
+    """Every stream to `seconds` of audio (one value or one per stream), two passes in one call: returns (list of outputs,
+    TwoPassBatch).  The lengths land as near the target as speedy_wave --length brings them: one correction step."""
+    plan = Plan(sample_rate, match_matlab)
+    ch = np.broadcast_to(np.asarray(channels, np.int32), (len(streams),))
+    lengths = [np.asarray(x).size // int(c) for x, c in zip(streams, ch)]
+    b = TwoPassBatch(plan, lengths, channels, 1.0, nonlinear, feedback, taps=taps, spectrogram_taps=spectrogram_taps, seconds=seconds)
     b.upload(streams)
     b.run()
     return b.results(), b

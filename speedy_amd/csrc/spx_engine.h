@@ -4,6 +4,7 @@
 //                   run_impl (decide with spx_mode.h, then launch), sub-batches, the rate call
 //   spx_mixed.hip   one call over several plans (BASELINE configs[4])
 //   spx_map.hip     the call with a time map, and the lookup
+//   spx_twopass.hip the two-pass call (a probe pass, then the final pass at a speed worked out on the device), its retarget kernel
 //   spx_convert.hip the call on float samples: two conversions around the int16 call
 //   spx_pipeline.hip the pipeline object: it includes this header for the entries it calls (spx_internal_run*, spx_conv_*)
 //   spx_diag.hip    kernel names, resource queries, timing collection, output packing, small copies
@@ -242,6 +243,18 @@ struct SpxRateCall {
   const int16_t* tsm_base = nullptr;                 // the base SpxRateJob::tsm_off counts from
   int max_blocks = 1;
 };
+// The second pass of a two-pass call (spx_batch_run_twopass, spx_twopass.hip): the speeds of the job table are not known on the host
+// -- a retarget kernel behind the staging kernel works them out from the first pass's counts (spx_twopass.h) and patches them into
+// the staged SpxStreamDev records.  Kernels in sequence on the caller's stream; the speed in the host table is a placeholder that
+// decides nothing.
+struct SpxRetargetCall {
+  std::vector<int> table;                // the SpxRetargetJob records, as the staging kernel copies them (32-bit words)
+  void* d_table = nullptr;               // DEVICE (workspace): where they go
+  const int64_t* n_probe = nullptr;      // DEVICE [n]: the first pass's counts
+  float* speeds = nullptr;               // DEVICE [n]: the second-pass speeds, for the caller
+};
+// spx_twopass.hip: one thread per stream; `copies` = the time chunks the call was cut into (streams holds copies * n records)
+void spx_launch_retarget(const void* d_table, int n, int copies, const int64_t* n_probe, float* speeds, SpxStreamDev* streams, hipStream_t st);
 // What every batch call is given (the arguments of spx_batch_run, in its order): the extern "C" entries fill one.
 struct SpxCall {
   spx_plan_t plan;
@@ -262,7 +275,11 @@ struct SpxCallOpts {
   // spx_batch_run_map: DEVICE, the call's time map (spx_map_rows per job, in job order).  Handled like a rate call: the whole batch on
   // the GENERAL walk kernel (its map instantiation; neither speed-up form writes a map), kernels in sequence on the caller's stream
   int64_t* map = nullptr;
-  bool ahead_req = false;      // spx_batch_run_ahead: pipelined with the plan's previous call where the shape allows
+  // spx_batch_run_twopass's second pass: the speeds come from the device.  Handled like a rate call and a map call -- kernels in
+  // sequence on the caller's stream -- but on the walk kernels' any-speed forms (the speed class is "any speed", whatever the
+  // placeholder in the host table says); with do_a = false the pass reuses the frame records the first pass left in the workspace
+  const SpxRetargetCall* retarget = nullptr;
+  bool ahead_req = false;     // spx_batch_run_ahead: pipelined with the plan's previous call where the shape allows
   bool overlap_req = false;    // spx_batch_run_overlapped: ... and its walk kernel beside the previous call's
   void* in_ready = nullptr;    // hipEvent_t: the producers wait for it (the caller's "input is there")
   bool split_part = false;     // one of the sub-batches run_split cut the call into (spx_batch_read_steps finds their state records by it)
@@ -283,7 +300,7 @@ SpxModeRuntime mode_runtime(spx_plan* plan);   // zeroed, with the plan's device
 spx_taps taps_advance(const spx_taps& t, int64_t rows, int64_t spec, int64_t norm);
 // what a call refuses about its job table (spx_jobs.h, then the walk kernel's LDS window), asked before anything is enqueued
 SpxJobLimits spx_job_limits(spx_plan_t plan);
-int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call = false, bool short_window = false);
+int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call = false, bool short_window = false, bool device_speeds = false);
 int spx_read_steps(const SpxPlanDev& d, const spx_stream_job* jobs, int n, const void* ws, int32_t* steps, hipStream_t st);
 
 // ---- what the pipeline object (spx_pipeline.hip) calls ----

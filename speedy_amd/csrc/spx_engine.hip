@@ -501,7 +501,7 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   // the choke point every call passes: a table that is refused has changed nothing of the plan and enqueued nothing
   // (general: the call runs on the general walk kernel whatever its speeds -- a rate call, a call with a time map)
   const bool general = opt.rate != nullptr || opt.map != nullptr;
-  if (spx_check_jobs(plan, jobs, n, general, force && force->no_exclusive)) return -1;
+  if (spx_check_jobs(plan, jobs, n, general, force && force->no_exclusive, opt.retarget != nullptr)) return -1;
   SpxRange range_(do_a && do_w ? "spx_batch_run" : (do_a ? "spx_batch_analyze" : "spx_batch_walk"));
   SpxPlanDev d = plan->dev;  // a copy: the tile size is chosen per call
   Layout L = layout_for(d, jobs, n);
@@ -510,7 +510,10 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   const int maxC = SC.maxC;
   // (a rate call: SPX_F_NO_TRUNC is the general walk kernel's -- neither speed-up form knows it -- so the whole call is the general kernel's)
   // (a time map: written by the general kernel's map instantiation alone -- the same rule)
-  const bool speedup_only = SC.speedup_only && !general, any_speed = SC.any_speed && !general;
+  // (a two-pass call's second pass: the speeds are worked out on the device -- "any speed", never a class read off the placeholder
+  // in the host table; spx_batch_run_twopass has refused a table whose device speeds could leave the range the any-speed forms serve)
+  const bool retarget = opt.retarget != nullptr;
+  const bool speedup_only = SC.speedup_only && !general && !retarget, any_speed = retarget ? !general : (SC.any_speed && !general);
   std::lock_guard<std::mutex> plan_lock(plan->mu);
   // a call that is not a sub-batch of run_split's leaves no split record for its workspace (spx_batch_analyze / _walk and mixed
   // calls come here directly: a stale record made spx_batch_read_steps look for sub-batch slices -- ADVICE r5)
@@ -529,7 +532,7 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   // ---- decide ----
   const SpxModeShape S = mode_shape(n, maxC, L.total_frames > 0, opt);
   SpxModeEnv E = mode_env();
-  if (general) E.concurrent_enabled = false;   // a rate call's kernels run in sequence on the caller's stream (the rate kernel ends it); a map call's too
+  if (general || retarget) E.concurrent_enabled = false;   // a rate call's kernels run in sequence on the caller's stream (the rate kernel ends it); a map call's and a retargeted pass's too
   SpxModeRuntime T = mode_runtime(plan);
   const int two_back = (plan->ahead_calls + SPX_RING - 2) % SPX_RING;
   T.two_workspaces = plan->ev_walk_valid[two_back] && plan->ring_ws[two_back] == ws;
@@ -562,6 +565,8 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   build_streams(d, jobs, n, nch, sv, tiles, opt.rate, opt.map != nullptr);
   if (opt.rate && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_rate: internal: not a plain call in sequence");
   if (opt.map && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force || opt.rate)) return fail(-1, "spx_batch_run_map: internal: not a plain call in sequence");
+  if (retarget && (concurrent || ahead || chunk_ahead || !do_w || force || opt.rate || opt.map || opt.ahead_req || opt.detached))
+    return fail(-1, "spx_batch_run_twopass: internal: not a plain call in sequence");
   if (opt.map && (R.walk.fast_kernel || spx_walk_config(d, {.n_streams = n, .max_channels = maxC}).mode != 0))
     return fail(-1, "spx_batch_run_map: internal: no general walk kernel for this batch");
   unsigned char* w = static_cast<unsigned char*>(ws);
@@ -573,7 +578,7 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   int* d_flags = reinterpret_cast<int*>(w + L.off_flags);
   int* d_ready = reinterpret_cast<int*>(w + L.off_ready);
   SpxTapsDev td = taps_of(taps);
-  const bool timed = g_timing.load() && do_a && do_w;
+  const bool timed = g_timing.load() && ((do_a && do_w) || retarget);   // (a two-pass call is timed as two calls)
   if (do_a && do_w) g_last_concurrent.store(concurrent ? 1 : (ahead ? 2 : 0), std::memory_order_relaxed);
   static const bool dbg_mode = getenv("SPX_DEBUG_MODE") != nullptr;   // one line per call: what was decided and why
   if (dbg_mode)
@@ -648,11 +653,17 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   // the staging kernel (same stream, nothing in between).
   const bool ahead_gate = ahead && !force && plan->ahead_started != nullptr && plan->ahead_n > 0 && !waited_prev &&
                           ring_previous_in_flight(plan);
-  // (a rate call is never concurrent: the tile order's place in the staging kernel carries its SpxRateJob records instead)
-  const int rc = stage_tables(plan, sv, opt.rate ? opt.rate->table : order, dstreams, opt.rate ? reinterpret_cast<int*>(opt.rate->d_table) : d_order, d_flags, concurrent ? (unsigned)tiles[0] : 0u, d_ready,
+  // (a rate call is never concurrent: the tile order's place in the staging kernel carries its SpxRateJob records instead; a
+  // retargeted pass's carries its SpxRetargetJob records)
+  const std::vector<int>& side_table = opt.rate ? opt.rate->table : (retarget ? opt.retarget->table : order);
+  int* const d_side_table = opt.rate ? reinterpret_cast<int*>(opt.rate->d_table) : (retarget ? static_cast<int*>(opt.retarget->d_table) : d_order);
+  const int rc = stage_tables(plan, sv, side_table, dstreams, d_side_table, d_flags, concurrent ? (unsigned)tiles[0] : 0u, d_ready,
                     (concurrent || ahead) ? (unsigned)n + 1u : 0u, (ahead || chunk_ahead) ? sa : st, &staged_ev,
                     ahead_gate ? plan->ahead_started : nullptr, plan->ahead_n, 8000u);
   if (rc) return rc;
+  // the second pass of a two-pass call: the speeds of every staged record (all nch copies of a stream's), from the first pass's
+  // counts -- right behind the staging kernel on the same stream, ahead of the tension kernel, the first reader of a speed
+  if (retarget) spx_launch_retarget(opt.retarget->d_table, n, nch, opt.retarget->n_probe, opt.retarget->speeds, dstreams, st);
   if (M.trial_slot >= 0) {  // bracket this call on the caller's stream (spx_plan::Trial)
     hipEvent_t& e0 = TR.ev[2 * M.trial_slot];
     if (!e0) HIPCHK(hipEventCreate(&e0));
@@ -828,9 +839,10 @@ int spx_internal_run(const SpxCall& c, bool ahead, bool overlap, void* in_ready,
 // What every batch call asks FIRST about its job table: the rules of spx_jobs.h for every job, then the one rule that needs a
 // kernel's resources -- the walk kernel's LDS window of the batch's shape.  Host arithmetic only: -1 with spx_last_error, and nothing
 // of the plan's state has changed; 0 and the call can fail on a HIP error only.
-// rate_call: at least one rate other than 1 (the general walk kernel's window); short_window: SpxForce::no_exclusive.
+// rate_call: at least one rate other than 1 (the general walk kernel's window); short_window: SpxForce::no_exclusive;
+// device_speeds: a two-pass call's second pass (SpxCallOpts::retarget) -- the any-speed forms' window, whatever the table's speeds.
 SpxJobLimits spx_job_limits(spx_plan_t plan) { return {plan->dev.W, plan->dev.B, spx_internal_analysis_fits(plan->dev)}; }
-int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call, bool short_window) {
+int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate_call, bool short_window, bool device_speeds) {
   if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
   const SpxJobLimits L = spx_job_limits(plan);
   for (int i = 0; i < n; i++) {
@@ -839,7 +851,8 @@ int spx_check_jobs(spx_plan_t plan, const spx_stream_job* jobs, int n, bool rate
   }
   const SpxSpeedClass SC = speed_class(jobs, n);
   std::lock_guard<std::mutex> plan_lock(plan->mu);
-  const SpxModeResources& R = mode_resources(plan, n, SC.maxC, SC.speedup_only && !rate_call, SC.any_speed && !rate_call, short_window);
+  const SpxModeResources& R = mode_resources(plan, n, SC.maxC, SC.speedup_only && !rate_call && !device_speeds,
+                                             device_speeds ? !rate_call : (SC.any_speed && !rate_call), short_window);
   if (R.walk.lds > 160 * 1024)   // one CU's LDS; the window holds every channel of maxRequired + 64 frames at least
     return fail(-1, "spx_batch: too many channels for the walk kernel's LDS window");
   return 0;

@@ -1,10 +1,11 @@
-// Host-only build of the launch-mode decision (spx_mode.h) for tests/test_mode_table.py and of the job rules (spx_jobs.h) for
-// tests/test_job_rules.py: plain g++, no HIP.  The mode query and its answer are flat arrays of 64-bit integers so that the Python
+// Host-only build of the launch-mode decision (spx_mode.h) for tests/test_mode_table.py, of the job rules (spx_jobs.h) for
+// tests/test_job_rules.py and of the two-pass call's speed formula (spx_twopass.h) for tests/test_twopass_abi.py: plain g++, no HIP.  The mode query and its answer are flat arrays of 64-bit integers so that the Python
 // side mirrors them by NAME (the two name lists below are exported).
 #include <string.h>
 
 #include "spx_jobs.h"
 #include "spx_mode.h"
+#include "spx_twopass.h"
 
 #define SPX_Q_FIELDS(X)                                                                                                         \
   X(n) X(max_channels) X(do_a) X(do_w) X(has_frames) X(forced) X(force_concurrent) X(force_ahead) X(force_total_streams)        \
@@ -119,5 +120,9 @@ int spx_mode_table_check_job(int W, int B, int analysis_fits, int channels, long
 }
 const char* spx_mode_table_job_fault_text(int code) {
   return code < SPX_JOB_OK || code > SPX_JOB_TOO_LONG ? "" : spx_job_fault_text(static_cast<SpxJobFault>(code));
+}
+// spx_twopass_speed: the second-pass speed the retarget kernel writes for one stream (the same text, compiled for the host)
+float spx_mode_table_twopass_speed(double want, int length_mode, long long n_in, long long n_probe) {
+  return spx_twopass_speed(want, length_mode, n_in, n_probe);
 }
 }
