@@ -3,6 +3,10 @@ API against the exact integer definition of the time-scale modification (tests/t
 full-scale, channel-distinct inputs of tests/tsm_inputs.py (what they reach: tests/test_oracle_tsm_definition.py,
 profiles/tsm_definition.txt).  Every case also asserts the walk form it ran on.  Integer equality, no tolerance.
 
+The drop-in API's rate stage (sonic2_api.hip, spx_rate_kernel) is held against tsm_ref.PlaybackStream call for call: rate changes
+in mid-stream, both lives, a rate first set behind unread output, one nonlinear life on the events its own speed callback
+reported, and the 16-channel limit.
+
 The definition's outputs are computed once per module (_WANT) and left unchanged.
 """
 import os
@@ -337,6 +341,203 @@ def test_the_stream_api_call_for_call_on_the_planted_event_lists(coalesce):
             assert form == ((132 if rate == 48000 else 68) if fast else 0), (name, coalesce, form)
         finally:
             s.close()
+
+
+def _playback_want(p):
+    """(the definition's final output, frames after each event) of a playback stream, once per module."""
+    key = ("playback", p[0])
+    if key not in _WANT:
+        s, counts = T.playback_events(p[1], p[2], p[3])
+        y = np.asarray(s.out, np.int64)
+        assert y.min() >= -32768 and y.max() <= 32767
+        y.setflags(write=False)
+        _WANT[key] = (y, counts)
+    return _WANT[key]
+
+
+def _playback_case(p, coalesce, own, hold=False):
+    """One playback stream through a fresh handle, event for event: ("rate", r) is sonicSetRate (own) / sonicIntSetRate, after which
+    nothing may appear; a write or a flush is followed by reads until nothing is left, which return exactly what the definition
+    produced in that event.  own: sonicSetSpeed / sonicWriteShortToStream / sonicFlushStream with the nonlinear factor 0; otherwise
+    the sonicInt* calls.  hold: nothing is read before the first write or flush behind the first sonicSetRate -- the handle enters rate
+    mode with everything it has produced so far unread."""
+    from speedy_amd.sonic2 import SonicStream
+    name, rate, ch, events = p
+    out, counts = _playback_want(p)
+    first_rate = [e[0] for e in events].index("rate")
+    prime_the_form_counter()
+    s = SonicStream(rate, ch, False, coalesce)
+    try:
+        s.enable_nonlinear(0.0)
+        done = 0
+        for k, ev in enumerate(events):
+            if ev[0] == "rate":
+                s.set_rate(ev[1]) if own else s.L.sonicIntSetRate(s.h, float(ev[1]))
+            elif own:
+                s.set_speed(ev[-1])
+                assert (s.write_short(ev[1]) if ev[0] == "write" else s.flush()) == 1, (name, k)
+            else:
+                s.int_set_speed(ev[-1])
+                assert (s.int_write_short(ev[1]) if ev[0] == "write" else s.int_flush()) == 1, (name, k)
+            if hold and k <= first_rate:
+                continue
+            got = _drain(s)
+            end = counts[k] * ch
+            assert got.size == end - done and np.array_equal(got, out[done:end]), (name, coalesce, own, k, ev[0], ev[-1], got.size // ch, (end - done) // ch)
+            done = end
+        assert done == out.size, name
+        assert s.L.spx_debug_last_walk_form() == 0, (name, coalesce, own)           # a handle with a rate: the general kernel
+    finally:
+        s.close()
+
+
+def _both_sides_of_one(events):
+    speeds = [e[-1] for e in events if e[0] != "rate"]
+    return min(speeds) < 1.0 < max(speeds)
+
+
+@pytest.mark.parametrize("coalesce", [True, False])
+@pytest.mark.parametrize("plan", range(len(I.RATE_PLANS)))
+def test_the_stream_api_with_rate_changes_through_both_lives(plan, coalesce):
+    """The planted event lists under one rate plan (tests/tsm_inputs.py RATE_PLANS) against tsm_ref.PlaybackStream, call for call
+    through BOTH lives: positions carried across the flush, sonicSetRate in mid-stream (to and from 1, to the value already set) with
+    a frame waiting, the rate first set behind three writes.  Every list goes through the stream's own calls with the nonlinear
+    factor 0; the lists with speeds on both sides of 1 go through the sonicInt* calls as well.  A handle with a rate leaves the
+    pool, so `coalesce` must make no difference -- it decides only what the handle was before.
+
+    Out of scope: a NONLINEAR second life with a rate -- the shim's partial ring buffer survives the flush, and the event list of
+    such a life has no closed form in tests/tsm_ref.py."""
+    streams = [p for p in I.playback_streams() if p[0].endswith("/plan%d" % plan)]
+    assert len(streams) == 8
+    through_int = 0
+    for p in streams:
+        _playback_case(p, coalesce, own=True)
+        if _both_sides_of_one(p[3]):
+            _playback_case(p, coalesce, own=False)
+            through_int += 1
+    assert through_int == 4, through_int
+
+
+DIRECTED = ("one_frame_calls", "stale_return", "sixteen_channels", "unread_head", "3999Hz", "44100Hz", "96000Hz")
+
+
+@pytest.mark.parametrize("coalesce", [True, False])
+@pytest.mark.parametrize("name", DIRECTED)
+def test_the_stream_api_on_the_directed_playback_streams(name, coalesce):
+    """One frame per call (the frame that waits is all the state there is), a return from 1 with a stale frame, 16 channels, 3 999 Hz,
+    44.1 kHz and 96 kHz -- through the stream's own calls and, where the speeds lie on both sides of 1, the sonicInt* calls."""
+    p = [q for q in I.playback_streams() if q[0] == name][0]
+    _playback_case(p, coalesce, own=True)
+    if _both_sides_of_one(p[3]):
+        _playback_case(p, coalesce, own=False)
+
+
+@pytest.mark.parametrize("coalesce", [True, False])
+def test_a_rate_first_set_behind_unread_output(coalesce):
+    """enter_rate_mode's copy of the unread head: nothing is read before the call behind the first sonicSetRate, then everything
+    produced so far must come out -- the speed stage's frames of the calls before the rate, unchanged, and the rate stage's behind
+    them.  The directed stream and the planted lists under the plan that sets the rate before event 3."""
+    streams = [p for p in I.playback_streams() if p[0] == "unread_head" or p[0].endswith("/plan1")]
+    assert len(streams) == 9
+    held = 0
+    for p in streams:
+        first = [e[0] for e in p[3]].index("rate")
+        assert first == 3, p[0]
+        held += int(_playback_want(p)[1][first] > 0)
+        _playback_case(p, coalesce, own=True, hold=True)
+    assert held == 7, held          # (the two speed-up lists have produced nothing by then: 320 frames, below maxRequired, no unity write)
+
+
+def _shim_speeds(orc, x, rate, ch, speed, nl, rates, chunk):
+    """The oracle shim under the same calls: the speeds its speed callback reported, per write."""
+    L = orc.lib()
+    spd = []
+    cb = orc.TENSION_FN(lambda s, t, v: spd.append(float(np.float32(v))))
+    h = L.orc_sonicCreateStream(rate, ch, 0)
+    L.orc_sonicSetSpeed(h, speed); L.orc_sonicEnableNonlinearSpeedup(h, nl); L.orc_sonicSetDurationFeedbackStrength(h, 0.0)
+    L.orc_sonicSpeedCallback(h, cb)
+    per_write = []
+    for w, pos in enumerate(range(0, x.size // ch, chunk)):
+        if w in rates:
+            L.orc_sonicSetRate(h, rates[w])
+        seg = np.ascontiguousarray(x[pos * ch:(pos + chunk) * ch])
+        before = len(spd)
+        assert L.orc_sonicWriteShortToStream(h, orc.sptr(seg), seg.size // ch) == 1
+        per_write.append(spd[before:])
+    L.orc_sonicDestroyStream(h)
+    return per_write
+
+
+@pytest.mark.parametrize("coalesce", [True, False])
+def test_a_nonlinear_stream_with_a_rate_and_a_rate_change(orc, coalesce):
+    """One life of a nonlinear stream (syllables, 16 kHz, 3.5x) with a rate from the start and another from write 7 on.  The events
+    of the definition are the shim's handoff list: buffer k (B frames) at the k-th speed that the stream's OWN speed callback
+    reported, in the write that reported it; the buffers left at the flush at the last speed; the trailing partial buffer dropped.
+    The speeds are asserted equal to the oracle shim's, write for write.  After every call the reads return what the definition
+    produced on that call's events."""
+    from speedy_amd.sonic2 import SonicStream
+    name, rate, ch, x, speed, nl = [j for j in I.nonlinear_jobs() if (j[1], j[2], j[4]) == (16000, 1, 3.5)][0]
+    B, chunk, rates = rate // 100, 1000, {0: 1.25, 7: 0.8}
+    n = x.size // ch
+    prime_the_form_counter()
+    s = SonicStream(rate, ch, False, coalesce)
+    spd, calls = [], []
+    try:
+        s.set_speed(speed); s.enable_nonlinear(nl); s.set_feedback(0.0)
+        s.on_speed(lambda t, v: spd.append(float(np.float32(v))))
+        for w, pos in enumerate(range(0, n, chunk)):
+            if w in rates:
+                s.set_rate(rates[w])
+            before = len(spd)
+            assert s.write_short(x[pos * ch:(pos + chunk) * ch]) == 1
+            calls.append((spd[before:], _drain(s)))
+        assert s.flush() == 1
+        tail = _drain(s)
+        assert s.L.spx_debug_last_walk_form() == 0
+    finally:
+        s.close()
+    assert [c[0] for c in calls] == _shim_speeds(orc, x, rate, ch, speed, nl, rates, chunk)
+    assert n % B != 0 and len(set(spd)) > 10 and 10 < sum(len(c[0]) for c in calls[:7]) < len(spd) - 10 and len(spd) < n // B
+    p = T.PlaybackStream(rate, ch)
+    k = 0
+    for w, (speeds, got) in enumerate(calls):
+        if w in rates:
+            p.set_rate(rates[w])
+        before = len(p.out)
+        for sp in speeds:
+            p.write(x[k * B * ch:(k + 1) * B * ch], sp)
+            k += 1
+        want_w = np.asarray(p.out[before:], np.int64)
+        assert got.size == want_w.size and np.array_equal(got, want_w), (w, got.size, want_w.size)
+    before = len(p.out)
+    while k < n // B:
+        p.write(x[k * B * ch:(k + 1) * B * ch], spd[-1])
+        k += 1
+    p.flush(spd[-1])
+    want_t = np.asarray(p.out[before:], np.int64)
+    print(name, "events", n // B, "frames", p.frames_out, p.census)
+    assert tail.size == want_t.size and np.array_equal(tail, want_t), (tail.size, want_t.size)
+    assert p.census["set_with_left"] == 1 and p.census["straddle"] >= 50 and p.frames_out > 2000, p.census
+
+
+def test_seventeen_channels_with_a_rate_are_refused_and_sixteen_work_right_after():
+    """SPX_RATE_MAX_CHANNELS: the write returns 0 and the error names the limit, again on the next write (nothing was half done);
+    a fresh 16-channel handle then produces the definition's stream."""
+    from speedy_amd.sonic2 import SonicStream
+    x = I.rectangles(16000, 17, 700)
+    s = SonicStream(16000, 17, False, False)
+    try:
+        s.enable_nonlinear(0.0)
+        s.set_speed(2.0)
+        s.set_rate(1.25)
+        for _ in range(2):
+            assert s.write_short(x) == 0
+            assert b"at most 16 channels" in s.L.speedyHipLastError()
+            assert s.read_short(64).size == 0
+        assert s.flush() == 0 and b"at most 16 channels" in s.L.speedyHipLastError()
+    finally:
+        s.close()
+    _playback_case([q for q in I.playback_streams() if q[0] == "sixteen_channels"][0], False, own=True)
 
 
 @pytest.mark.parametrize("coalesce", [True, False])

@@ -7,6 +7,10 @@ hands the TSM stage the closed-form event list and its output is the definition'
 requirements on the inputs, asserted from the definition alone; every switch of the definition (one mistake each) changes the
 output of some directed input.  All comparisons are integer equality.
 
+The rate stage as a stream (tsm_ref.PlaybackStream; tsm_inputs.playback_streams: sonicSetRate in mid-stream, second lives, a stale
+frame, one-frame calls) has a section of its own: the oracle after every call, the census per stream, one named stream per switch,
+and the one equivalent switch (no_wrap), which must change nothing.
+
 SPX_TSM_CENSUS=<path> writes the census table (profiles/tsm_definition.txt).
 """
 import os
@@ -157,6 +161,9 @@ class _Int:
             got.append(self.buf[:k * self.ch].copy())
 
     def call(self, ev):
+        if ev[0] == "rate":
+            self.L.orc_sonicIntSetRate(self.h, ev[1])
+            return self.read()
         self.L.orc_sonicIntSetSpeed(self.h, ev[-1])
         if ev[0] == "write":
             x = np.ascontiguousarray(ev[1], np.int16)
@@ -366,7 +373,7 @@ def test_unity_clears_remaining_and_flush_resets_prev_cannot_show_in_a_linear_jo
     assert _linear_differs(linear, names, "flush_resets_prev") is None
 
 
-@pytest.mark.parametrize("switch", T.RATE_SWITCHES)
+@pytest.mark.parametrize("switch", T.CLOSED_FORM_SWITCHES)
 def test_every_rate_stage_switch_changes_a_rate_jobs_output(rated, switch):
     caught = []
     for name, hz, ch, x, speed, rate in I.rate_jobs():
@@ -380,14 +387,210 @@ def test_every_rate_stage_switch_changes_a_rate_jobs_output(rated, switch):
 
 
 def test_every_switch_has_a_test():
-    covered = set(TEETH) | {"unity_clears_remaining", "flush_resets_prev"} | set(T.RATE_SWITCHES)
+    covered = set(TEETH) | {"unity_clears_remaining", "flush_resets_prev"} | set(T.CLOSED_FORM_SWITCHES) | set(PLAYBACK_TEETH) | {"no_wrap"}
     assert covered == set(T.SWITCHES)
+
+
+# ------------------------------------------------------------------ the rate stage as a stream ------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def playback():
+    """{name: (the definition's PlaybackStream, frames after each event)} of every playback stream; computed once, left unchanged."""
+    return {name: T.playback_events(hz, ch, ev) for name, hz, ch, ev in I.playback_streams()}
+
+
+N_PLAYBACK = 8 * 4 + 7          # the eight planted lists under the four rate plans, seven directed cases
+
+
+def test_the_playback_streams_are_the_planted_lists_under_every_plan_and_the_directed_cases():
+    streams = I.playback_streams()
+    assert len(streams) == N_PLAYBACK == len(I.planted_streams()) * len(I.RATE_PLANS) + 7
+    assert len({s[0] for s in streams}) == N_PLAYBACK
+    for (name, hz, ch, ev), k in zip(streams, range(len(I.planted_streams()) * len(I.RATE_PLANS))):
+        pname, phz, pch, pev = I.planted_streams()[k // len(I.RATE_PLANS)]
+        plan = I.RATE_PLANS[k % len(I.RATE_PLANS)]
+        assert name == "%s/plan%d" % (pname, k % len(I.RATE_PLANS)) and (hz, ch) == (phz, pch)
+        assert [e for e in ev if e[0] != "rate"] == pev, name                                   # the planted events, in order
+        rates = [e[1] for e in ev if e[0] == "rate"]
+        assert rates == [float(plan[i]) for i in sorted(plan) if i < len(pev)] and rates, name
+        assert len(rates) == len(plan) or pname != "planted22k", name    # (shorter lists: the later indices plant nothing)
+    for name, hz, ch, ev in streams:
+        kinds = [e[0] for e in ev]
+        assert kinds.count("flush") == 2 and kinds[-1] == "flush" and "rate" in kinds, name
+        assert sum(e[1].size for e in ev if e[0] == "write") // ch <= 30000, name
+    by = {s[0]: s for s in streams}
+    assert by["sixteen_channels"][2] == 16 and {by[n][1] for n in ("3999Hz", "44100Hz", "96000Hz")} == {3999, 44100, 96000}
+    ev = by["one_frame_calls"][3]
+    assert ev[0] == ("rate", 0.8) and [e[1].size // 2 for e in ev[1:41]] == [1] * 40 and all(e[2] == 1.0 for e in ev[1:41])
+    ev = by["unread_head"][3]
+    assert [e[0] for e in ev[:4]] == ["write", "write", "write", "rate"]
+
+
+def test_the_playback_stream_with_one_life_is_the_closed_form(rated):
+    """The rate set before the first write, one write, one flush: the sequential definition equals rate_stage's closed form on every
+    directed rate job, after the write and after the flush."""
+    for name, hz, ch, x, speed, rate in I.rate_jobs():
+        s, counts = T.playback_events(hz, ch, [("rate", rate), ("write", x, speed), ("flush", speed)])
+        assert counts[1:] == [rated[name].frames_after_write, rated[name].frames_out] and s.out == rated[name].out, name
+        assert s.census["rate_neg_frac"] == rated[name].census["rate_neg_frac"], name
+
+
+def test_oracle_equals_the_definition_on_every_playback_stream(orc, playback):
+    """orc_sonicInt* after EVERY call -- orc_sonicIntSetRate included, after which nothing may appear -- in count and samples."""
+    seen = 0
+    for name, hz, ch, ev in I.playback_streams():
+        s, counts = playback[name]
+        assert counts[-1] > 0, name
+        _call_for_call(orc, hz, ch, ev, s.out, counts, name)
+        seen += 1
+    assert seen == N_PLAYBACK
+
+
+def test_the_shims_nonlinear_stream_with_a_rate_is_the_definition_on_its_handoff_list(orc):
+    """One nonlinear life (syllables, 16 kHz, 3.5x) with a rate from the start and another from write 7 on: after every write the
+    shim's reads are what PlaybackStream produces on the buffers handed over in that write (B frames each, at the speed handed with
+    them), sonicSetRate falling between the same two events; at the flush the remaining whole buffers at the last speed."""
+    L = orc.lib()
+    name, rate, ch, x, speed, nl = [j for j in I.nonlinear_jobs() if (j[1], j[2], j[4]) == (16000, 1, 3.5)][0]
+    B, rates, n = rate // 100, {0: 1.25, 7: 0.8}, x.size // ch
+    handed = []
+    cb = orc.HANDOFF_FN(lambda s, t, sp, buf, frames: handed.append((float(np.float32(sp)), np.ctypeslib.as_array(buf, shape=(frames * ch,)).copy())))
+    h = L.orc_sonicCreateStream(rate, ch, 0)
+    L.orc_sonicSetSpeed(h, speed); L.orc_sonicEnableNonlinearSpeedup(h, nl); L.orc_sonicSetDurationFeedbackStrength(h, 0.0)
+    L.orc_sonicHandoffCallback(h, cb)
+    buf = np.zeros((1 << 16) * ch, np.int16)
+
+    def drain():
+        got = []
+        while True:
+            k = L.orc_sonicReadShortFromStream(h, orc.sptr(buf), 1 << 16)
+            if k <= 0:
+                return np.concatenate(got).astype(np.int64) if got else np.zeros(0, np.int64)
+            got.append(buf[:k * ch].copy())
+    p = T.PlaybackStream(rate, ch)
+    for w, pos in enumerate(list(range(0, n, 1000)) + [None]):
+        if w in rates:
+            L.orc_sonicSetRate(h, rates[w])
+            p.set_rate(rates[w])
+        before_ev, before_out = len(handed), len(p.out)
+        if pos is None:
+            assert L.orc_sonicFlushStream(h) == 1
+        else:
+            seg = np.ascontiguousarray(x[pos * ch:(pos + 1000) * ch])
+            assert L.orc_sonicWriteShortToStream(h, orc.sptr(seg), seg.size // ch) == 1
+        for sp, b in handed[before_ev:]:
+            p.write(b, sp)
+        if pos is None:
+            p.flush(handed[-1][0])
+        got, want = drain(), np.asarray(p.out[before_out:], np.int64)
+        assert got.size == want.size and np.array_equal(got, want), (w, got.size, want.size)
+    L.orc_sonicDestroyStream(h)
+    assert len(handed) == n // B and all(np.array_equal(b, x[k * B * ch:(k + 1) * B * ch]) for k, (_, b) in enumerate(handed))
+    assert p.census["set_with_left"] == 1 and p.census["straddle"] >= 50 and p.frames_out > 2000, p.census
+
+
+# What each stream reaches, counted by the definition alone: (wraps, set_with_left, bypass_flush_with_left, stale_used,
+# life_starts_off_zero, short_calls).  Wraps: 22.05 kHz needs the rates 3.0 and 1.1 (old = 11 025 input frames in one life), 48 kHz
+# wraps at old = 12 000, 3 999 Hz at 3 999.
+REACHES = {
+    "planted22k/plan0": (0, 4, 0, 1, 1, 0), "planted22k/plan1": (0, 1, 1, 0, 0, 0),
+    "planted22k/plan2": (1, 1, 1, 0, 1, 0), "planted22k/plan3": (1, 0, 0, 0, 1, 0),
+    "planted16k_stereo/plan0": (0, 3, 1, 0, 0, 0), "planted16k_stereo/plan1": (0, 1, 1, 0, 0, 0),
+    "planted16k_stereo/plan2": (0, 1, 1, 0, 1, 0), "planted16k_stereo/plan3": (0, 0, 0, 0, 1, 0),
+    "planted16k_near_unity/plan0": (0, 1, 0, 0, 1, 0), "planted16k_near_unity/plan1": (0, 1, 1, 0, 0, 0),
+    "planted16k_near_unity/plan2": (0, 0, 0, 0, 1, 0), "planted16k_near_unity/plan3": (0, 0, 0, 0, 1, 0),
+    "planted48k/plan0": (0, 2, 0, 0, 0, 0), "planted48k/plan1": (1, 1, 1, 0, 0, 0),
+    "planted48k/plan2": (2, 1, 1, 0, 1, 0), "planted48k/plan3": (2, 0, 0, 0, 1, 0),
+    "speedup22k/plan0": (0, 3, 1, 0, 0, 0), "speedup22k/plan1": (0, 1, 1, 0, 0, 0),
+    "speedup22k/plan2": (0, 1, 1, 0, 1, 0), "speedup22k/plan3": (1, 0, 0, 0, 1, 0),
+    "speedup48k_stereo/plan0": (0, 2, 0, 0, 1, 0), "speedup48k_stereo/plan1": (1, 1, 1, 0, 0, 0),
+    "speedup48k_stereo/plan2": (1, 0, 0, 0, 1, 0), "speedup48k_stereo/plan3": (1, 0, 0, 0, 1, 0),
+    "second_life_hum22k/plan0": (0, 0, 0, 0, 1, 0), "second_life_hum22k/plan1": (0, 0, 0, 0, 0, 0),
+    "second_life_hum22k/plan2": (0, 0, 0, 0, 1, 0), "second_life_hum22k/plan3": (0, 0, 0, 0, 1, 0),
+    "second_life_hum16k/plan0": (0, 0, 0, 0, 1, 0), "second_life_hum16k/plan1": (0, 0, 0, 0, 0, 0),
+    "second_life_hum16k/plan2": (0, 0, 0, 0, 1, 0), "second_life_hum16k/plan3": (0, 0, 0, 0, 1, 0),
+    "one_frame_calls": (0, 0, 0, 0, 1, 2), "stale_return": (0, 4, 1, 1, 0, 0), "sixteen_channels": (0, 1, 0, 0, 1, 0),
+    "unread_head": (0, 0, 0, 0, 1, 0), "3999Hz": (1, 1, 0, 0, 1, 0), "44100Hz": (1, 1, 0, 0, 1, 0), "96000Hz": (1, 0, 0, 0, 0, 0),
+}
+
+
+def test_what_every_playback_stream_reaches(playback):
+    """Requirements on the INPUTS, from the definition alone.  Per stream the six structural counts, exactly; then what the directed
+    cases are for."""
+    keys = ("wraps", "set_with_left", "bypass_flush_with_left", "stale_used", "life_starts_off_zero", "short_calls")
+    assert set(REACHES) == set(playback) and len(playback) == N_PLAYBACK
+    for name, (s, _) in playback.items():
+        assert s.census.keys() == dict.fromkeys(T.PLAYBACK_CENSUS).keys(), name
+        assert tuple(s.census[k] for k in keys) == REACHES[name], (name, s.census)
+    for k in T.PLAYBACK_CENSUS:                                                   # every count is reached somewhere
+        assert sum(s.census[k] for s, _ in playback.values()) >= 1, k
+    c = {name: s.census for name, (s, _) in playback.items()}
+    # one frame per call: the first call of each life only sets the waiting frame; every output of a write has operands from two
+    # calls (the flush's padded call, 2 maxRequired zero frames at once, emits the rest)
+    s, counts = playback["one_frame_calls"]
+    ev = {p[0]: p[3] for p in I.playback_streams()}["one_frame_calls"]
+    writes = [k for k, e in enumerate(ev) if e[0] == "write"]
+    assert c["one_frame_calls"]["short_calls"] == 2 and counts[writes[0]] == 0
+    assert c["one_frame_calls"]["straddle"] >= sum(counts[k] - counts[k - 1] for k in writes[1:]) >= 55
+    assert c["stale_return"]["stale_used"] == 1 and c["planted22k/plan0"]["stale_used"] == 1
+    assert c["stale_return"]["bypass_flush_with_left"] == 1
+    assert c["sixteen_channels"]["rate_neg_frac"] >= 1000 and c["sixteen_channels"]["straddle"] >= 2
+    assert c["44100Hz"]["halving_dropped"] >= 1 and c["96000Hz"]["halving_dropped"] == 0 and c["96000Hz"]["wraps"] == 1
+    assert c["planted48k/plan1"]["halving_dropped"] == 0          # (48 000 / 0.5, / 2.0: even all the way down)
+    assert c["planted22k/plan3"]["halving_dropped"] >= 1          # 22 050 / 1.1 = 20 045: the halving drops a bit of `new`
+    for name in playback:
+        if name.startswith(("planted", "speedup")):
+            assert c[name]["straddle"] >= 1, name
+    # no two channels of the 16-channel output are equal
+    y = np.asarray(playback["sixteen_channels"][0].out, np.int64).reshape(-1, 16)
+    assert y.shape[0] > 5000 and len({y[:, a].tobytes() for a in range(16)}) == 16
+
+
+# The stream that each switch is shown on (the others it changes: profiles/tsm_definition.txt)
+PLAYBACK_TEETH = {
+    "flush_resets_positions": "planted22k/plan3",          # the second life starts at positions != 0 and no sonicSetRate follows
+    "flush_keeps_left": "unread_head",
+    "set_rate_keeps_positions": "planted22k/plan0",
+    "set_rate_drops_left": "stale_return",
+    "same_rate_is_noop": "planted22k/plan0",               # 1.5 set again at event 27
+    "unity_rate_drops_left": "stale_return",
+    "flush_count_without_left": "one_frame_calls",
+    "straddle_uses_new_left": "one_frame_calls",
+}
+
+
+def _playback_caught(playback, switch):
+    """The streams whose output, or whose count after some event, the switch changes; every stream is visited."""
+    caught, seen = [], 0
+    for name, hz, ch, ev in I.playback_streams():
+        m, counts = T.playback_events(hz, ch, ev, switch)
+        if m.out != playback[name][0].out or counts != playback[name][1]:
+            caught.append(name)
+        seen += 1
+    assert seen == N_PLAYBACK
+    return caught
+
+
+@pytest.mark.parametrize("switch", sorted(PLAYBACK_TEETH))
+def test_every_playback_switch_changes_a_named_stream(playback, switch):
+    assert PLAYBACK_TEETH[switch] in _playback_caught(playback, switch), switch
+
+
+def test_no_wrap_is_equivalent_and_changes_nothing(playback):
+    """In unbounded integers (o, k) and (o + old, k + new) give the same loop test (o + 1) new > k old and the same ratio
+    (o + 1) new - k old, and k == new whenever o reaches old: a stage that never returns to 0 computes the same stream.  (In 32-bit
+    arithmetic it would overflow after 2^31 / 2^14 input frames: the return to 0 is what keeps the products small.)  Shown on streams
+    that do wrap."""
+    assert len(set(PLAYBACK_TEETH) | {"no_wrap"}) == len(T.PLAYBACK_SWITCHES) == 9 and set(PLAYBACK_TEETH) | {"no_wrap"} == set(T.PLAYBACK_SWITCHES)
+    assert sum(1 for s, _ in playback.values() if s.census["wraps"]) >= 10
+    assert _playback_caught(playback, "no_wrap") == []
 
 
 # ------------------------------------------------------------------ the table ------------------------------------------------------------------
 
-def test_census_table(linear, planted, rated, nonlinear):
-    """The census of every directed input; written to SPX_TSM_CENSUS when that is set (profiles/tsm_definition.txt)."""
+def test_census_table(linear, planted, rated, nonlinear, playback):
+    """The census of every directed input; written to SPX_TSM_CENSUS when that is set (profiles/tsm_definition.txt).  The playback
+    streams follow in a table of their own (PLAYBACK_CENSUS), then the streams that each PlaybackStream switch changes."""
     rows = []
     for name, rate, ch, x, speed in I.linear_jobs():
         if not name.startswith("run"):
@@ -411,4 +614,12 @@ def test_census_table(linear, planted, rated, nonlinear):
             f.write("%-44s %7s %5s " % ("input", "frames", "steps") + " ".join("%10s" % k for k in short) + "\n")
             for name, frames, steps, c in rows:
                 f.write("%-44s %7d %5d " % (name, frames, steps) + " ".join("%10d" % c[k] for k in T.CENSUS) + "\n")
+            pshort = ("wraps", "set_left", "byp_flush", "stale", "off_zero", "short", "straddle", "r_neg_frac", "halv_drop")
+            f.write("\n%-44s %7s %5s " % ("playback stream", "frames", "steps") + " ".join("%10s" % k for k in pshort) + "\n")
+            for name, (s, _) in playback.items():
+                f.write("%-44s %7d %5d " % (name, s.frames_out, s.speed_stage.steps) + " ".join("%10d" % s.census[k] for k in T.PLAYBACK_CENSUS) + "\n")
+            f.write("\n")
+            for sw in T.PLAYBACK_SWITCHES:
+                caught = _playback_caught(playback, sw)
+                f.write("%-26s changes %2d of %d: %s\n" % (sw, len(caught), len(playback), " ".join(caught) if caught else "none (equivalent)"))
             f.writelines(ln for ln in notes if ln.startswith("#"))      # (the GPU file's wall time, noted by hand, stays)

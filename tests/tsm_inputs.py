@@ -137,6 +137,74 @@ def planted_streams():
     return _PLANTED
 
 
+# Rate plans over the planted event lists: {index of the planted event BEFORE which sonicSetRate is called: the rate}.  An index past
+# the end of a list (the two second_life lists have four events) plants nothing.
+RATE_PLANS = ({0: 1.25, 9: 0.8, 16: 1.0, 20: 1.5, 27: 1.5},     # both sides of 1, back to 1 and away again, the value already set
+              {3: 0.5, 12: 1.0, 25: 2.0},                        # the rate first set after three writes; through 1 in the middle
+              {0: 3.0, 30: 1.0},
+              {0: 1.1})
+_PLAYBACK = None
+
+
+def with_rates(events, plan):
+    out = []
+    for k, ev in enumerate(events):
+        if k in plan:
+            out.append(("rate", float(plan[k])))
+        out.append(ev)
+    return out
+
+
+def _calls(rate, ch, calls):
+    """[("rate", r) | ("flush", speed) | (frames, speed)] over consecutive pieces of the rectangles."""
+    total = sum(c[0] for c in calls if c[0] not in ("rate", "flush"))
+    x = rectangles(rate, ch, total)
+    ev, pos = [], 0
+    for c in calls:
+        if c[0] in ("rate", "flush"):
+            ev.append((c[0], float(c[1])))
+        else:
+            ev.append(("write", x[pos * ch:(pos + c[0]) * ch], float(c[1])))
+            pos += c[0]
+    return ev
+
+
+def playback_streams():
+    """[(name, rate_hz, channels, events)] for the rate stage as a stream: the planted event lists (two lives each) under every rate
+    plan, then the directed cases.  Events: the planted ones and ("rate", r)."""
+    global _PLAYBACK
+    if _PLAYBACK is not None:
+        return _PLAYBACK
+    out = []
+    for name, rate, ch, ev in planted_streams():
+        for i, plan in enumerate(RATE_PLANS):
+            out.append(("%s/plan%d" % (name, i), rate, ch, with_rates(ev, plan)))
+    # one frame per call at speed 1: the first call of a life only sets the waiting frame, every later call emits one or two frames
+    # whose operands come from two calls
+    out.append(("one_frame_calls", 16000, 2, _calls(16000, 2, [("rate", 0.8)] + [(1, 1.0)] * 40 + [("flush", 1.0)] + [(1, 1.0)] * 9
+                                                           + [("flush", 1.0)])))
+    # back from 1 to a rate != 1 with a frame gone stale; a flush at 1 with that frame waiting; the value already set, set again
+    out.append(("stale_return", 16000, 1, _calls(16000, 1, [("rate", 0.8), (300, 1.0), ("rate", 1.0), (200, 1.0), (1, 1.0), ("rate", 1.25),
+                                                           (300, 1.0), (900, 2.0), ("rate", 1.25), (150, 1.0), ("rate", 1.0), (50, 1.0),
+                                                           ("flush", 1.0), (100, 1.0), ("rate", 0.8), (700, 2.0), (120, 1.0),
+                                                           ("flush", 1.0)])))
+    # 16 channels, the most a rate != 1 supports; no two channels equal
+    out.append(("sixteen_channels", 16000, 16, _calls(16000, 16, [("rate", 1.25), (2500, 2.0), (700, 1.0), ("rate", 0.8), (1500, 0.7),
+                                                                  ("flush", 0.7), (900, 1.0), ("flush", 1.0)])))
+    # the rate first set behind several writes: on the device nothing is read before the write that follows it
+    out.append(("unread_head", 22050, 1, _calls(22050, 1, [(1500, 2.0), (700, 1.0), (2100, 1.3), ("rate", 1.25), (1800, 2.0), (400, 1.0),
+                                                           ("flush", 1.0), (2000, 2.0), ("flush", 2.0)])))
+    # 3 999 Hz (the direct search; old = 3 999 wraps inside the stream), 44.1 kHz (the halving drops a bit of `new`), 96 kHz
+    out.append(("3999Hz", 3999, 1, _calls(3999, 1, [("rate", 1.1), (1000, 0.7), (1000, 0.7), (1000, 0.7), ("flush", 0.7), (500, 2.0),
+                                                    ("rate", 0.8), (499, 2.0), ("flush", 2.0)])))
+    out.append(("44100Hz", 44100, 2, _calls(44100, 2, [("rate", 1.1), (5000, 1.3), (4000, 1.0), (4230, 2.0), ("flush", 2.0), (6000, 1.3),
+                                                       ("rate", 0.7), (6000, 1.0), ("flush", 1.0)])))
+    out.append(("96000Hz", 96000, 1, _calls(96000, 1, [("rate", 0.8), (9000, 2.0), (10800, 1.0), ("flush", 1.0), ("rate", 1.25), (9000, 2.0),
+                                                       ("flush", 2.0)])))
+    _PLAYBACK = out
+    return out
+
+
 def syllables(rate, channels, frames):
     """The rectangles under a 4 Hz raised-cosine envelope (full scale at the crests, silence between them): the nonlinear
     speed-up's speed moves with it, so that consecutive 10 ms events carry different speeds."""

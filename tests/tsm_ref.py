@@ -21,8 +21,22 @@ linear_job / nonlinear_job -- what a batch job is in terms of that stream.  The 
 (pinned by tests/features_ref.py and the bit-exact taps).
 
 rate_stage / rate_job -- the rate stage (sonicSetRate) of ONE life cycle -- the rate set before the first write, one flush -- in
-closed form over the speed stage's uncut output.  OUT OF SCOPE: a second life behind a flush with a rate != 1, where the stage's two
-positions carry over; second lives are covered for the speed stage only.
+closed form over the speed stage's uncut output.
+
+PlaybackStream -- the rate stage as a stream, the sequential form of the same text (the dependency's adjustRate, interpolate,
+sonicSetRate and sonicFlushStream; anchors in oracle/orc_sonic.h): set_rate(r) at any time, any number of lives.  It fixes
+  * set_rate: the rate is stored and both positions return to 0, always -- also for the value already set; waiting frames stay;
+  * after each process call the frames that call appended: at rate 1 straight to the output, positions and pitch buffer untouched
+    (a frame waiting there goes stale); otherwise appended to the pitch buffer and, for pos in 0 .. M - 2: while (o + 1) new > k old
+    emit (ratio p[pos] + (new - ratio) p[pos + 1]) / new per channel, truncated toward zero, ratio = (o + 1) new - k old, k += 1;
+    then o += 1, and at o == old both positions return to 0; the consumed frames leave the buffer, one stays;
+  * the flush: expected = out + (int)((pending / speed + waiting) / rate + 0.5f) in float32 BEFORE the padding, `waiting` the pitch
+    buffer's frame count, a stale frame included; the padded call; the output cut to `expected` if it is longer; the pitch buffer
+    emptied; the positions KEPT.
+PINNED by it, on the CPU against the oracle and on the device against the drop-in API: second lives with a rate, rate changes in
+the middle of a stream (to and from 1, to the value already set), a rate first set behind unread output, one-frame calls.  What
+REMAINS outside: a NONLINEAR second life with a rate (the shim's partial ring buffer survives the flush; the event list of such a
+life has no closed form here), and pitch / volume / chord pitch, which the project does not implement.
 
 The switches make one mistake each (SWITCHES); the tests use them to show that the directed inputs have teeth:
   xfade_floor   floor for truncation          copy_uncapped           one piece of `remaining`
@@ -33,6 +47,13 @@ The switches make one mistake each (SWITCHES); the tests use them to show that t
   rate_floor    floor for truncation          rate_swapped      weights exchanged
   rate_no_halving  the rates are not halved   rate_keeps_last   emits while t <= M - 1, repeating the last frame
   rate_flush_floor no + 0.5 in the rate stage's flush count
+and PlaybackStream's (PLAYBACK_SWITCHES):
+  flush_resets_positions   the flush zeroes o and k        flush_keeps_left         the flush keeps the waiting frame
+  set_rate_keeps_positions set_rate leaves o and k         set_rate_drops_left      set_rate empties the pitch buffer
+  same_rate_is_noop        set_rate(the value set) does nothing                     unity_rate_drops_left    a call at rate 1 empties it
+  flush_count_without_left `expected` without `waiting`    straddle_uses_new_left   a frame that straddles two calls takes its left
+  no_wrap                  the positions never return to 0 at o == old              operand from the new call's first frame
+no_wrap is EQUIVALENT in unbounded integers: (o, k) and (o + old, k + new) give the same loop test and the same ratio.
 """
 import numpy as np
 
@@ -40,11 +61,17 @@ import pitch_ref as R
 
 SPEED_SWITCHES = ("xfade_floor", "xfade_swapped", "xfade_late", "copy_uncapped", "unity_clears_remaining", "flush_floor",
                   "flush_after_pad", "flush_pad_short", "flush_no_cut", "flush_resets_prev")
-RATE_SWITCHES = ("rate_floor", "rate_swapped", "rate_no_halving", "rate_keeps_last", "rate_flush_floor")
+CLOSED_FORM_SWITCHES = ("rate_floor", "rate_swapped", "rate_no_halving", "rate_keeps_last", "rate_flush_floor")     # rate_stage / RateStream
+PLAYBACK_SWITCHES = ("flush_resets_positions", "flush_keeps_left", "set_rate_keeps_positions", "set_rate_drops_left", "same_rate_is_noop",
+                     "unity_rate_drops_left", "flush_count_without_left", "straddle_uses_new_left", "no_wrap")           # PlaybackStream
+RATE_SWITCHES = CLOSED_FORM_SWITCHES + PLAYBACK_SWITCHES
 SWITCHES = SPEED_SWITCHES + RATE_SWITCHES
 
 CENSUS = ("xfade_neg_frac", "xfade_full", "pad_kept", "copy_capped", "inherits_copy", "unity_with_remaining", "failed_steps",
           "flush_cut", "flush_uncut", "flush_tie", "rate_neg_frac", "halving_dropped")
+# PlaybackStream's own counts.  halving_dropped: process calls at a rate != 1 whose (new, old) lost a bit to the halving
+PLAYBACK_CENSUS = ("wraps", "set_with_left", "bypass_flush_with_left", "stale_used", "life_starts_off_zero", "short_calls", "straddle",
+                   "rate_neg_frac", "halving_dropped")
 
 _F = np.float32
 
@@ -285,6 +312,126 @@ class RateStream:
         expected = before + int(v)
         full = rate_stage(s.out, self.C, self.new, self.old, self.switch, self.census)
         self.out = full[:expected * self.C] if len(full) // self.C > expected else full
+
+
+class PlaybackStream:
+    """SpeedStream with the rate stage behind it AS A STREAM: set_rate(r) at any time, write(frames, speed), flush(speed), any number
+    of lives.  `out` is the final output so far, `census` counts what the calls reached (PLAYBACK_CENSUS).
+
+    The state is the float32 rate (1 at creation), the two positions o (input frames passed) and k (output frames emitted) since
+    they were last zeroed, and the pitch buffer: the frames that wait for a right neighbour.  After every process call of the speed
+    stage -- a write, or the flush's padded call -- the stage takes what that call appended (_take)."""
+
+    def __init__(self, rate_hz, channels, switch=None):
+        assert switch is None or switch in SWITCHES, switch
+        self.speed_stage = SpeedStream(rate_hz, channels, switch if switch in SPEED_SWITCHES else None)
+        self.rate_hz, self.C, self.switch = rate_hz, channels, switch
+        self.playback = _F(1.0)
+        self.o = self.k = 0
+        self.pitch = []                        # waiting frames, each a list of C Python integers
+        self.out = []
+        self.census = dict.fromkeys(PLAYBACK_CENSUS, 0)
+        self._stale = False                    # the waiting frame was passed by while the rate was 1
+        self._life_begins = True               # no process call yet in this life
+
+    @property
+    def frames_out(self):
+        return len(self.out) // self.C
+
+    def set_rate(self, r):
+        r = _F(r)
+        if self.pitch:
+            self.census["set_with_left"] += 1
+        if self.switch == "same_rate_is_noop" and r == self.playback:
+            return
+        self.playback = r
+        if self.switch != "set_rate_keeps_positions":
+            self.o = self.k = 0
+        if self.switch == "set_rate_drops_left":
+            self.pitch, self._stale = [], False
+
+    def _take(self, fresh):
+        """fresh: what the speed stage appended in this process call, interleaved."""
+        C, cen, sw = self.C, self.census, self.switch
+        begins, self._life_begins = self._life_begins, False
+        if self.playback == _F(1.0):
+            self.out += fresh
+            if self.pitch:
+                self._stale = True
+                if sw == "unity_rate_drops_left":
+                    self.pitch, self._stale = [], False
+            return
+        if begins and (self.o or self.k):
+            cen["life_starts_off_zero"] += 1
+        new, old = rate_pair(self.rate_hz, self.playback, None, cen)
+        had = len(self.pitch)                  # 0 or 1: the frame an earlier call left behind
+        p = self.pitch
+        p += [fresh[i:i + C] for i in range(0, len(fresh), C)]
+        M = len(p)
+        if M < 2:
+            if fresh:
+                cen["short_calls"] += 1
+            return
+        for pos in range(M - 1):
+            across = pos == 0 and had > 0
+            left, right = (p[1] if across and sw == "straddle_uses_new_left" else p[pos]), p[pos + 1]
+            while (self.o + 1) * new > self.k * old:
+                ratio = (self.o + 1) * new - self.k * old
+                if across:
+                    cen["straddle"] += 1
+                    if self._stale:
+                        cen["stale_used"] += 1
+                for c in range(C):
+                    num = ratio * left[c] + (new - ratio) * right[c]
+                    if num < 0 and num % new:
+                        cen["rate_neg_frac"] += 1
+                    self.out.append(tdiv(num, new))
+                self.k += 1
+            self.o += 1
+            if self.o == old and sw != "no_wrap":
+                self.o = self.k = 0
+                cen["wraps"] += 1
+        del p[:M - 1]
+        self._stale = False
+
+    def write(self, frames, speed):
+        s = self.speed_stage
+        before = len(s.out)
+        s.write(frames, speed)
+        self._take(s.out[before:])
+
+    def flush(self, speed):
+        s = self.speed_stage
+        waiting = 0 if self.switch == "flush_count_without_left" else len(self.pitch)
+        v = _F(_F(_F(s.pending) / _F(speed)) + _F(waiting)) / self.playback + _F(0.5)
+        expected = self.frames_out + int(v)
+        if self.playback == _F(1.0) and self.pitch:
+            self.census["bypass_flush_with_left"] += 1
+        before = len(s.out)
+        s.flush(speed, cut=False)
+        self._take(s.out[before:])
+        if self.frames_out > expected:
+            del self.out[expected * self.C:]
+        if self.switch != "flush_keeps_left":
+            self.pitch, self._stale = [], False
+        if self.switch == "flush_resets_positions":
+            self.o = self.k = 0
+        self._life_begins = True
+
+
+def playback_events(rate_hz, channels, events, switch=None):
+    """A PlaybackStream over [("rate", r) | ("write", samples, speed) | ("flush", speed)]: (stream, frames produced after each event)."""
+    s = PlaybackStream(rate_hz, channels, switch)
+    counts = []
+    for ev in events:
+        if ev[0] == "rate":
+            s.set_rate(ev[1])
+        elif ev[0] == "write":
+            s.write(ev[1], ev[2])
+        else:
+            s.flush(ev[1])
+        counts.append(s.frames_out)
+    return s, counts
 
 
 def rate_job(x, rate_hz, channels, speed, rate, switch=None):
