@@ -151,7 +151,14 @@ int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, f
  *   inverse  u clamped to [0, Y[L-1]]; u >= Y[L-1] gives n_in; else j = the largest index with Y[j] <= u (a flat run resolves
  *            to its last node, so Y[j+1] > u) and  X[j] + (u - Y[j]) * (X[j+1] - X[j]) / (Y[j+1] - Y[j])
  * Both are non-decreasing, and forward(inverse(u)) <= u.  Returns 0, or -1 (spx_last_error) for a null pointer or a table
- * spx_batch_run refuses. */
+ * spx_batch_run refuses.
+ * DOMAIN: the lookups are exact where n_in * Y[L-1] < 2^63.  Precisely: neither product exceeds its segment's
+ * (X[j+1] - X[j]) * (Y[j+1] - Y[j]) -- the forward one reaches it in the last segment, at t = n_in, and stays below it elsewhere
+ * (t < X[j+1] there); the inverse one stops at (Y[j+1] - Y[j] - 1) times the segment's width -- so the answers are exact while that
+ * product is at most 2^63 - 1 in every segment; a segment is at most n_in wide (R = 0) or 2B - 1 (R >= 1) and rises by at most
+ * Y[L-1].  Every map spx_batch_run_map writes lies far inside (n_in < 2^30, and the walk kernel counts at most 2^31 - 1 output
+ * frames).  Outside the domain, and on rows that decrease or are negative, the answers are unspecified; the indices stay inside
+ * the stream's rows and no divisor is zero. */
 int64_t spx_plan_map_rows(spx_plan_t plan, int64_t n_in, float nonlinear);
 int spx_batch_run_map(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int16_t* in,
                       int16_t* out, int64_t* n_out, int64_t* map, void* workspace, size_t workspace_bytes,
@@ -518,6 +525,13 @@ void spx_set_tension_form(int form);
 /* Diagnostics: the tension kernel the last batch call of this process launched, 0 = spx_tension_kernel, 1 = spx_tension_seq_kernel
  * (the streaming and unit-level APIs always launch the former and leave this value alone). */
 int spx_debug_last_tension_form(void);
+/* Diagnostics: the number of time chunks the last whole batch call of this process (analysis and walk in one call: spx_batch_run and
+ * its _rate, _map, _float, _twopass, _ahead and _overlapped forms) ran in -- 1, 2 above two streams per CU, or what
+ * spx_set_pipeline_chunks asked for; 0 before the first such call. */
+int spx_debug_last_call_chunks(void);
+/* Diagnostics: the query blocks per stream of the last spx_map_lookup of this process (4 .. 1 024); *launches (may be NULL) = the
+ * kernel launches it took (one per 65 535 streams); 0 before the first call. */
+int spx_debug_last_lookup_grid(int* launches);
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls);
 /* "analysis;tension;walk": the kernels (template arguments included, as a profiler prints them) that serve a batch of
  * n_streams streams with at most max_channels channels; speedup_only = every job has speed > 1. */

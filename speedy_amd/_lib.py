@@ -86,6 +86,8 @@ SYMBOLS = {
     "spx_set_concurrent": (None, [C.c_int]),
     "spx_set_tension_form": (None, [C.c_int]),
     "spx_debug_last_tension_form": (C.c_int, []),
+    "spx_debug_last_call_chunks": (C.c_int, []),
+    "spx_debug_last_lookup_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_timing_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "spx_timing_last_tension_ms": (C.c_double, []),
     "spx_timing_last_rate_ms": (C.c_double, []),

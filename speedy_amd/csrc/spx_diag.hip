@@ -80,6 +80,7 @@ void spx_set_timing(int enabled) { g_timing = enabled != 0; }
 void spx_set_concurrent(int on) { g_concurrent = on != 0; }
 void spx_set_tension_form(int form) { g_tension_form = form != 0; }
 int spx_debug_last_tension_form(void) { return g_last_tension_form.load(std::memory_order_relaxed); }
+int spx_debug_last_call_chunks(void) { return g_last_call_chunks.load(std::memory_order_relaxed); }
 void spx_set_pipeline_chunks(int chunks) { g_chunks_set = true; g_chunks = chunks < 1 ? 1 : (chunks > SPX_MAX_CHUNKS ? SPX_MAX_CHUNKS : chunks); }
 static double g_last_tension_ms = 0.0, g_last_rate_ms = 0.0;
 double spx_timing_last_tension_ms(void) { return g_last_tension_ms; }

@@ -157,6 +157,7 @@ extern std::atomic<int> g_last_concurrent;   // spx_debug_last_call_concurrent (
 extern std::atomic<int> g_concurrent;        // spx_set_concurrent
 extern std::atomic<int> g_tension_form;      // spx_set_tension_form
 extern std::atomic<int> g_last_tension_form; // spx_debug_last_tension_form (run_impl alone sets it)
+extern std::atomic<int> g_last_call_chunks;  // spx_debug_last_call_chunks (run_impl alone sets it)
 extern std::atomic<bool> g_chunks_set;       // the caller chose a chunk count (spx_set_pipeline_chunks)
 extern std::atomic<int> g_chunks;
 extern std::mutex g_tmu;

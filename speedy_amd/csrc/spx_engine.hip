@@ -26,6 +26,7 @@ std::atomic<int> g_last_concurrent{0};   // spx_debug_last_call_concurrent (2 = 
 std::atomic<int> g_concurrent{1};  // spx_set_concurrent: analysis and walk kernels on two streams, tile-flag hand-off
 std::atomic<int> g_tension_form{0};       // spx_set_tension_form: 1 = spx_tension_kernel for every launch
 std::atomic<int> g_last_tension_form{SPX_TENSION_POLL};   // spx_debug_last_tension_form
+std::atomic<int> g_last_call_chunks{0};   // spx_debug_last_call_chunks
 std::atomic<bool> g_chunks_set{false};  // the caller chose a chunk count (spx_set_pipeline_chunks)
 std::atomic<int> g_chunks{1};  // spx_set_pipeline_chunks (measured on MI355X, 256 x 10 s: 1 -> 5.09 ms, 2 -> 5.25, 4 -> 5.54 per step)
 std::mutex g_tmu;
@@ -580,6 +581,7 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   SpxTapsDev td = taps_of(taps);
   const bool timed = g_timing.load() && ((do_a && do_w) || retarget);   // (a two-pass call is timed as two calls)
   if (do_a && do_w) g_last_concurrent.store(concurrent ? 1 : (ahead ? 2 : 0), std::memory_order_relaxed);
+  if (do_a && do_w) g_last_call_chunks.store(nch, std::memory_order_relaxed);
   static const bool dbg_mode = getenv("SPX_DEBUG_MODE") != nullptr;   // one line per call: what was decided and why
   if (dbg_mode)
     fprintf(stderr, "[spx mode] rate %d n %d maxC %d: co_resident %d doubtful %d lean %d want_concurrent %d chunks %d tiles %d -> %s%s\n",

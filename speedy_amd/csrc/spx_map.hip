@@ -73,7 +73,14 @@ spx_map_lookup_kernel(const SpxMapStream* __restrict__ streams, int stream0, int
   }
 }
 
+static std::atomic<int> g_last_lookup_gx{0}, g_last_lookup_launches{0};   // spx_debug_last_lookup_grid
+
 extern "C" {
+
+int spx_debug_last_lookup_grid(int* launches) {
+  if (launches) *launches = g_last_lookup_launches.load(std::memory_order_relaxed);
+  return g_last_lookup_gx.load(std::memory_order_relaxed);
+}
 
 int64_t spx_plan_map_rows(spx_plan_t plan, int64_t n_in, float nonlinear) {
   if (!plan || n_in < 0) { fail(-1, "spx_plan_map_rows: bad arguments"); return -1; }
@@ -118,6 +125,8 @@ int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n, const int
   // handful for many (a thread strides over what is left)
   int gx = 4096 / n;
   gx = gx < 4 ? 4 : (gx > 1024 ? 1024 : gx);
+  g_last_lookup_gx.store(gx, std::memory_order_relaxed);
+  g_last_lookup_launches.store((n + 65534) / 65535, std::memory_order_relaxed);
   for (int s0 = 0; s0 < n; s0 += 65535) {   // (the grid's second dimension holds 65 535)
     const int m = n - s0 < 65535 ? n - s0 : 65535;
     hipLaunchKernelGGL(spx_map_lookup_kernel, dim3((unsigned)gx, (unsigned)m), dim3(SPX_MAP_THREADS), 0, st,

@@ -226,6 +226,58 @@ def test_a_nonlinear_stereo_slow_down_job(orc):
     _nonlinear_case(orc, 16000, 2, 16 * 4 + 4, None, "spx_walk_fast_kernel<4, 4, 0, 0, 3>")
 
 
+def _nonlinear_map_case(orc, rate):
+    """Every nonlinear job of one sample rate (tsm_inputs.nonlinear_jobs and nonlinear_map_jobs; 1, 2, 3 and 8 channels side by side
+    at 16 kHz) in ONE spx_batch_run_map call with taps: the speed tap equals the oracle's, the output is the definition's on the
+    events the call's OWN speed tap gives, and the rows are the definition's rows (tsm_ref.nonlinear_job: frames_out immediately
+    before each event's write, then the final count) -- the `if constexpr (MAP)` stores of walk_body against the header's text,
+    not against the oracle.  The call runs the general kernel's map instantiation (form 0, the counter primed).
+
+    A map call cannot meet run_impl's "no general walk kernel for this batch": it asks spx_walk_config without a speed class, and
+    walk_mode then answers 0 for every channel count.  So every count is taken, and the test asserts that it is."""
+    jobs = [j for j in I.nonlinear_jobs() + I.nonlinear_map_jobs() if j[1] == rate]
+    assert jobs
+    from speedy_amd.batch import Batch, Plan
+    prime_the_form_counter()
+    plan = Plan(rate, False)
+    try:
+        b = Batch(plan, [j[3].size // j[2] for j in jobs], [j[2] for j in jobs], [j[4] for j in jobs], [j[5] for j in jobs], 0.0, taps=True,
+                  time_map=True)
+        b.upload([j[3] for j in jobs])
+        b.d_map.fill_(-12345)
+        b.run()
+        outs = b.results()
+        form, chunks = plan.L.spx_debug_last_walk_form(), plan.L.spx_debug_last_call_chunks()
+        print(rate, "Hz map call:", len(jobs), "jobs, channels", sorted({j[2] for j in jobs}), "form", form, "chunks", chunks)
+        assert form == 0 and chunks == 1, (form, chunks)
+        nout = b.d_nout.cpu().numpy()
+        for i, (job, _, ch, x, speed, nl) in enumerate(jobs):
+            tap = b.tap_arrays(i)["speed"]
+            ref = orc.compress_sound(x, rate, ch, speed, nl, 0.0, False, chunk=1000, taps=True)
+            assert np.array_equal(tap, ref["speed"]), job
+            n = x.size // ch
+            speeds = T.event_speeds(n, rate, tap, speed)
+            key = ("map", job, tap.tobytes())
+            if key not in _WANT:
+                s = T.nonlinear_job(x, rate, ch, speeds, speed)
+                _WANT[key] = (np.asarray(s.out, np.int64), list(s.rows))
+            w_out, w_rows = _WANT[key]
+            got = b.time_map(i)
+            print(job, "frames", outs[i].size // ch, w_out.size // ch, "rows", got.size)
+            assert outs[i].size == w_out.size and np.array_equal(outs[i], w_out), (job, outs[i].size, w_out.size)
+            assert got.tolist() == w_rows, (job, [k for k, (a, c) in enumerate(zip(got.tolist(), w_rows)) if a != c][:4])
+            assert got.size == n // plan.B + 1 and got[-1] == nout[i] and (n < plan.B or got[0] == 0) and (np.diff(got) >= 0).all(), job
+        assert b.map_offs[-1] == b.d_map.numel()
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("rate", sorted({j[1] for j in I.nonlinear_jobs() + I.nonlinear_map_jobs()}))
+def test_the_rows_of_nonlinear_jobs_are_the_definitions(orc, rate):
+    """11.025, 16, 22.05 and 48 kHz; at 16 kHz: n_in = R B, R B + B - 1, R = 1, n_in < B, a slow-down job, 1 / 2 / 3 / 8 channels."""
+    _nonlinear_map_case(orc, rate)
+
+
 def test_the_map_calls_walk_instantiation():
     """spx_batch_run_map: the general walk kernel's map instantiation writes the same int16 output.  (spx_batch_kernel_names speaks of
     the plain call only: the map kernel has no name to ask for; the form counter is primed instead.)"""

@@ -11,7 +11,12 @@ The rate stage as a stream (tsm_ref.PlaybackStream; tsm_inputs.playback_streams:
 frame, one-frame calls) has a section of its own: the oracle after every call, the census per stream, one named stream per switch,
 and the one equivalent switch (no_wrap), which must change nothing.
 
-SPX_TSM_CENSUS=<path> writes the census table (profiles/tsm_definition.txt).
+The time map's rows (tsm_ref.nonlinear_job(...).rows: frames_out before each event's write, then the final count) have a section
+too: the oracle's rows through its hand-off callback on every nonlinear job, in one piece and in pieces of 1000 frames; what the
+rows reach, from the definition alone; two mutants of the row definition, each changing a named job.
+
+SPX_TSM_CENSUS=<path> writes the census table (profiles/tsm_definition.txt), SPX_TIME_MAP_CENSUS=<path> the rows' table
+(profiles/time_map_definition.txt).
 """
 import os
 
@@ -584,6 +589,155 @@ def test_no_wrap_is_equivalent_and_changes_nothing(playback):
     assert len(set(PLAYBACK_TEETH) | {"no_wrap"}) == len(T.PLAYBACK_SWITCHES) == 9 and set(PLAYBACK_TEETH) | {"no_wrap"} == set(T.PLAYBACK_SWITCHES)
     assert sum(1 for s, _ in playback.values() if s.census["wraps"]) >= 10
     assert _playback_caught(playback, "no_wrap") == []
+
+
+# ------------------------------------------------------------------ the time map's rows ------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def mapped(orc, nonlinear):
+    """{name: (job, event speeds from the oracle's speed tap, the definition's stream with its rows)} of every nonlinear job: the
+    six above (their streams are the `nonlinear` fixture's) and tsm_inputs.nonlinear_map_jobs()."""
+    out = {}
+    for job in I.nonlinear_jobs() + I.nonlinear_map_jobs():
+        name, rate, ch, x, speed, nl = job
+        tap = orc.compress_sound(x, rate, ch, speed, nl, 0.0, False, chunk=1000, taps=True)["speed"]
+        speeds = T.event_speeds(x.size // ch, rate, tap, speed)
+        if name in nonlinear:
+            s = nonlinear[name][2]
+            assert speeds == [sp for sp, _ in nonlinear[name][1]], name
+        else:
+            s = T.nonlinear_job(x, rate, ch, speeds, speed)
+        out[name] = (job, speeds, s)
+    return out
+
+
+def _census_of_rows(rows, B):
+    """What a job's rows reach: the longest run of equal rows that does not start at row 0, whether the two rows directly before
+    the last are equal, the largest rise between consecutive rows, and M[0] = M[1] = 0."""
+    best = start = 0                    # maximal runs by the index they start at; the run that starts at row 0 does not count
+    for k in range(1, len(rows) + 1):
+        if k == len(rows) or rows[k] != rows[start]:
+            if start > 0:
+                best = max(best, k - start)
+            start = k
+    return dict(flat_run=best, flat_before_last=len(rows) >= 3 and rows[-3] == rows[-2],
+                largest_rise=max([b - a for a, b in zip(rows, rows[1:])] or [0]), starts_flat=len(rows) >= 2 and rows[0] == rows[1] == 0)
+
+
+MAP_JOB = "map/%dHz/%dch/%d/%g/%g"
+
+
+def test_the_map_jobs_are_the_shapes_the_rows_are_defined_on():
+    by = {j[0]: j for j in I.nonlinear_map_jobs()}
+    assert len(by) == len(I.nonlinear_map_jobs()) == 9 and not set(by) & {j[0] for j in I.nonlinear_jobs()}
+    shape = {name: (rate // 100, x.size // ch) for name, rate, ch, x, speed, nl in by.values()}
+    for name, rate, ch, x, speed, nl in by.values():
+        assert x.dtype == np.int16 and x.size // ch <= 1.5 * rate and nl != 0, name
+    B, n = shape[MAP_JOB % (16000, 1, 8000, 3.5, 1)]
+    assert n % B == 0 and n // B == 50                                         # n_in = R B exactly
+    B, n = shape[MAP_JOB % (16000, 1, 6559, 1.2, 1)]
+    assert n % B == B - 1                                                      # n_in = R B + B - 1
+    B, n = shape[MAP_JOB % (16000, 1, 200, 3.5, 1)]
+    assert B <= n < 2 * B                                                      # R = 1
+    B, n = shape[MAP_JOB % (16000, 1, 100, 3.5, 1)]
+    assert n < B                                                               # no complete buffer
+    assert {j[2] for j in by.values()} >= {1, 3, 8} and {j[1] for j in by.values()} == {11025, 16000, 48000}
+    assert by[MAP_JOB % (16000, 1, 9000, 0.5, 1)][4] == 0.5
+
+
+@pytest.mark.parametrize("chunk", [None, 1000], ids=["one piece", "chunks of 1000"])
+def test_the_definitions_rows_are_the_oracles(orc, mapped, chunk):
+    """frames_out immediately before each event's write, then the final count behind the flush -- the header's text, stated over
+    tests/tsm_ref.py's stream -- equals what the oracle stream reports through its hand-off callback (tests/time_map_ref.py), for
+    every nonlinear job, written in one piece and in pieces of 1000 frames; the output too."""
+    import time_map_ref as tm
+    assert len(mapped) == 15
+    for name, (job, speeds, s) in mapped.items():
+        _, rate, ch, x, speed, nl = job
+        B, n = rate // 100, x.size // ch
+        rows, times, out = tm.oracle_map(orc, x, rate, ch, speed, nl, False, 0.0, chunk=chunk)
+        assert len(s.rows) == n // B + 1 == tm.map_rows(B, n, nl), name
+        assert s.rows == rows.tolist(), (name, [k for k, (a, b) in enumerate(zip(s.rows, rows.tolist())) if a != b][:4])
+        assert s.rows[-1] == s.frames_out and np.array_equal(np.asarray(s.out, np.int64), out.astype(np.int64)), name
+        assert all(a <= b for a, b in zip(s.rows, s.rows[1:])) and (n < B or s.rows[0] == 0), name
+        if B <= n < 2 * B:                 # R = 1: no analysis frame, the event runs at the job's speed
+            assert speeds == [float(np.float32(speed))], name
+
+
+def test_linear_jobs_have_the_final_count_alone(linear):
+    for name, rate, ch, x, speed in I.linear_jobs():
+        assert linear[name].rows == [linear[name].frames_out] == T.linear_rows(linear[name]), name
+
+
+# What the rows reach, from the definition alone: the job each condition is asserted on (all jobs: profiles/time_map_definition.txt)
+ROWS_REACH = {
+    "flat_run": MAP_JOB % (16000, 1, 8000, 3.5, 1),             # 3 or more equal rows, not from row 0
+    "flat_before_last": MAP_JOB % (16000, 1, 6559, 1.2, 1),     # two equal rows directly before the last row
+    "rise_above_B": MAP_JOB % (16000, 1, 9000, 0.5, 1),         # a segment that rises by more than B
+    "starts_flat": MAP_JOB % (16000, 1, 6559, 1.2, 1),          # M[0] = 0 with M[1] = 0
+}
+
+
+def test_what_the_rows_reach(mapped):
+    c = {name: _census_of_rows(s.rows, job[1] // 100) for name, (job, _, s) in mapped.items()}
+    assert c[ROWS_REACH["flat_run"]]["flat_run"] >= 3, c[ROWS_REACH["flat_run"]]
+    assert c[ROWS_REACH["flat_before_last"]]["flat_before_last"], mapped[ROWS_REACH["flat_before_last"]][2].rows[-4:]
+    assert mapped[ROWS_REACH["flat_before_last"]][2].rows[-2] > 0          # (not the zeros the rows begin with)
+    assert c[ROWS_REACH["rise_above_B"]]["largest_rise"] > 160, c[ROWS_REACH["rise_above_B"]]
+    assert c[ROWS_REACH["starts_flat"]]["starts_flat"], mapped[ROWS_REACH["starts_flat"]][2].rows[:3]
+
+
+ROW_TEETH = {"row_after_write": MAP_JOB % (16000, 1, 8000, 3.5, 1), "row_before_cut": MAP_JOB % (16000, 1, 8000, 3.5, 1)}
+
+
+@pytest.mark.parametrize("switch", T.ROW_SWITCHES)
+def test_every_row_mutant_changes_a_named_jobs_rows(mapped, switch):
+    """Teeth: a count taken behind the event's write instead of before it, and a last row taken before the flush's cut, each
+    change the rows of the job named -- a kernel with that mistake cannot write the definition's rows there."""
+    assert set(ROW_TEETH) == set(T.ROW_SWITCHES)
+    job, speeds, s = mapped[ROW_TEETH[switch]]
+    _, rate, ch, x, speed, nl = job
+    m = T.nonlinear_job(x, rate, ch, speeds, speed, row_switch=switch)
+    assert m.rows != s.rows and len(m.rows) == len(s.rows), switch
+    if switch == "row_before_cut":
+        assert m.rows[:-1] == s.rows[:-1] and m.rows[-1] > s.rows[-1]
+    else:
+        assert m.rows[:-2] == s.rows[1:-1] and m.rows[-1] == s.rows[-1]        # every row but the last moves up by one event
+
+
+def _rows_caught(mapped, switch):
+    caught = []
+    for name, (job, speeds, s) in mapped.items():
+        _, rate, ch, x, speed, nl = job
+        if T.nonlinear_job(x, rate, ch, speeds, speed, row_switch=switch).rows != s.rows:
+            caught.append(name)
+    return caught
+
+
+def test_time_map_table(mapped):
+    """The rows' census per job and what each mutant changes; written to SPX_TIME_MAP_CENSUS when that is set
+    (profiles/time_map_definition.txt; lines that start with # -- the legend and the device's figures, noted by hand -- stay, in
+    front of the table)."""
+    path = os.environ.get("SPX_TIME_MAP_CENSUS")
+    rows = []
+    for name, (job, _, s) in mapped.items():
+        B, n = job[1] // 100, job[3].size // job[2]
+        c = _census_of_rows(s.rows, B)
+        R = n // B
+        rows.append((name, R, (n - (R - 1) * B) if R >= 1 else n, s.frames_out, c))
+    assert len(rows) == 15
+    if path:
+        notes = [ln for ln in open(path)] if os.path.exists(path) else []
+        with open(path, "w") as f:
+            f.writelines(ln for ln in notes if ln.startswith("#"))      # the legend and the device's figures first
+            f.write("\n%-36s %4s %5s %5s %7s %9s %16s %8s %11s\n" % ("job", "B", "R", "last", "frames", "flat_run", "flat_before_last", "max_rise", "starts_flat"))
+            for name, R, last, frames, c in rows:
+                f.write("%-36s %4d %5d %5d %7d %9d %16d %8d %11d\n" % (name, mapped[name][0][1] // 100, R, last, frames, c["flat_run"],
+                                                                    c["flat_before_last"], c["largest_rise"], c["starts_flat"]))
+            f.write("\n")
+            for sw in T.ROW_SWITCHES:
+                caught = _rows_caught(mapped, sw)
+                f.write("%-16s changes %2d of %d (asserted on %s): %s\n" % (sw, len(caught), len(mapped), ROW_TEETH[sw], " ".join(caught)))
 
 
 # ------------------------------------------------------------------ the table ------------------------------------------------------------------

@@ -1,8 +1,13 @@
-"""The time map's definition, on the CPU (include/speedy_hip.h "TIME MAP"): the oracle's rows, and the lookups in numpy int64.
+"""The time map's definition, on the CPU (include/speedy_hip.h "TIME MAP"): the oracle's rows, and the lookups in numpy int64 and
+-- ExactMap, forward_exact, inverse_exact -- in Python integers, written from the header's text and not from the numpy functions
+(tests/test_time_map_lookup_definition.py asserts that the two agree inside the domain).  The rows' own definition, which reads
+no oracle, is tests/tsm_ref.py's (nonlinear_job(...).rows).
 
 Rows.  The oracle stream is observed, not changed: orc_sonicHandoffCallback fires when ring buffer k is about to be handed to the
 time-scale stage, and inside the callback orc_sonicIntSamplesAvailable is the number of output frames produced so far (no audio is
 read before the end, so the count is the running total).  After orc_sonicFlushStream the count is read once more: the last row."""
+import bisect
+
 import numpy as np
 
 # the shapes the definition was pinned on: (sample rate, channels, speed, nonlinear, n_in)
@@ -71,6 +76,62 @@ def nodes(M, B, n_in, nl):
         return np.concatenate([np.arange(R, dtype=np.int64) * B, [n_in]]).astype(np.int64), M.copy()
     assert M.size == 1
     return np.asarray([0, n_in], np.int64), np.asarray([0, M[0]], np.int64)
+
+
+class ExactMap:
+    """The lookups in Python integers (unbounded; // on non-negative operands; bisect_right), written from the text of
+    include/speedy_hip.h "TIME MAP" and from nothing else:
+      Nodes: X = [0, B, .., (R-1)B, n_in], Y = M for R >= 1;  X = [0, n_in], Y = [0, M[0]] for R = 0.  L = the number of nodes.
+      forward  t clamped to [0, n_in]; n_in = 0 gives 0; else j = min(t / B, L - 2) and
+               Y[j] + (t - X[j]) * (Y[j+1] - Y[j]) / (X[j+1] - X[j])
+      inverse  u clamped to [0, Y[L-1]]; u >= Y[L-1] gives n_in; else j = the largest index with Y[j] <= u and
+               X[j] + (u - Y[j]) * (X[j+1] - X[j]) / (Y[j+1] - Y[j])
+    R = n_in / B for a nonlinear job, 0 for a linear one.  The rows must not decrease and must not be negative."""
+
+    def __init__(self, M, B, n_in, nl):
+        M = [int(v) for v in M]
+        self.B, self.n_in = int(B), int(n_in)
+        R = self.n_in // self.B if nl != 0 else 0
+        if R >= 1:
+            assert len(M) == R + 1
+            self.X, self.Y = [k * self.B for k in range(R)] + [self.n_in], M
+        else:
+            assert len(M) == 1
+            self.X, self.Y = [0, self.n_in], [0, M[0]]
+        assert all(a <= b for a, b in zip(self.Y, self.Y[1:])) and self.Y[0] >= 0, "rows outside the definition"
+        self.L = len(self.X)
+
+    def forward(self, t):
+        t = min(max(int(t), 0), self.n_in)
+        if self.n_in == 0:
+            return 0
+        X, Y = self.X, self.Y
+        j = min(t // self.B, self.L - 2)
+        return Y[j] + (t - X[j]) * (Y[j + 1] - Y[j]) // (X[j + 1] - X[j])
+
+    def inverse(self, u):
+        X, Y = self.X, self.Y
+        u = min(max(int(u), 0), Y[-1])
+        if u >= Y[-1]:
+            return self.n_in
+        j = bisect.bisect_right(Y, u) - 1
+        return X[j] + (u - Y[j]) * (X[j + 1] - X[j]) // (Y[j + 1] - Y[j])
+
+    def largest_product(self):
+        """The largest value either product can take over all queries: max over segments of width x rise (the domain's bound)."""
+        return max((self.X[j + 1] - self.X[j]) * (self.Y[j + 1] - self.Y[j]) for j in range(self.L - 1))
+
+
+def forward_exact(M, B, n_in, nl, t):
+    """Input frame -> output frame for every t of a sequence, as a list of Python integers."""
+    m = ExactMap(M, B, n_in, nl)
+    return [m.forward(v) for v in t]
+
+
+def inverse_exact(M, B, n_in, nl, u):
+    """Output frame -> input frame for every u of a sequence, as a list of Python integers."""
+    m = ExactMap(M, B, n_in, nl)
+    return [m.inverse(v) for v in u]
 
 
 def forward(M, B, n_in, nl, t):

@@ -231,6 +231,30 @@ def nonlinear_jobs():
     return _NONLINEAR
 
 
+# The time map's nonlinear jobs (a list of its own: the names above stay what they were).  B = rate // 100, R = frames // B:
+# (rate, channels, frames, speed, nonlinear factor, what the job is for)
+_MAP_SPECS = ((16000, 1, 8000, 3.5, 1.0, "n_in = R B exactly"),
+              (16000, 1, 6559, 1.2, 1.0, "n_in = R B + B - 1"),
+              (16000, 1, 200, 3.5, 1.0, "R = 1: no analysis frame, the one event runs at the job's speed"),
+              (16000, 1, 100, 3.5, 1.0, "n_in < B: no event, the final count alone"),
+              (16000, 3, 6000, 2.0, 1.0, "3 channels"),
+              (16000, 8, 4000, 3.5, 1.0, "8 channels"),
+              (16000, 1, 9000, 0.5, 1.0, "slow-down: rows that rise by more than B"),
+              (11025, 1, 6000, 3.0, 1.0, "11.025 kHz"),
+              (48000, 1, 24100, 2.0, 1.0, "48 kHz"))
+_MAP_JOBS = None
+
+
+def nonlinear_map_jobs():
+    """[(name, rate, channels, samples, speed, nonlinear factor)] -- the jobs the time map's rows are defined on, in addition to
+    nonlinear_jobs(): syllables, at most 1.5 s each."""
+    global _MAP_JOBS
+    if _MAP_JOBS is None:
+        _MAP_JOBS = [("map/%dHz/%dch/%d/%g/%g" % spec[:5], spec[0], spec[1], syllables(*spec[:3]), spec[3], spec[4])
+                     for spec in _MAP_SPECS]
+    return _MAP_JOBS
+
+
 _RATE = None
 
 

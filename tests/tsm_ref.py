@@ -18,7 +18,9 @@ SpeedStream -- the speed stage as a stream: write(frames, speed), flush(speed), 
     output cut to `expected` only if it is longer, input and `remaining` cleared, prevPeriod and prevMinDiff kept.
 
 linear_job / nonlinear_job -- what a batch job is in terms of that stream.  The event speeds of a nonlinear job are DATA here
-(pinned by tests/features_ref.py and the bit-exact taps).
+(pinned by tests/features_ref.py and the bit-exact taps).  Both record `rows`, the job's TIME MAP as include/speedy_hip.h words it:
+frames_out immediately before each event's write, then the final count behind the flush; a linear job, or a nonlinear one without
+a complete buffer, has the final count alone.  ROW_SWITCHES are the two mistakes a kernel could make there.
 
 rate_stage / rate_job -- the rate stage (sonicSetRate) of ONE life cycle -- the rate set before the first write, one flush -- in
 closed form over the speed stage's uncut output.
@@ -214,12 +216,18 @@ class SpeedStream:
             self.prev_period = 0
 
 
+def linear_rows(s):
+    """The time-map rows of a linear job (include/speedy_hip.h "TIME MAP"): the final count alone."""
+    return [s.frames_out]
+
+
 def linear_job(x, rate, channels, speed, switch=None):
-    """One write of everything at the job's speed, then the flush.  Returns the stream."""
+    """One write of everything at the job's speed, then the flush.  Returns the stream; `rows` beside it."""
     s = SpeedStream(rate, channels, switch)
     s.write(x, speed)
     s.frames_after_write = s.frames_out
     s.flush(speed)
+    s.rows = linear_rows(s)
     return s
 
 
@@ -231,16 +239,33 @@ def event_speeds(n_in, rate, tap, job_speed):
     return [tap[i] if i < len(tap) else (tap[-1] if tap else float(job_speed)) for i in range(k)]
 
 
-def nonlinear_job(x, rate, channels, speeds, job_speed=1.0, switch=None):
+ROW_SWITCHES = ("row_after_write", "row_before_cut")
+
+
+def nonlinear_job(x, rate, channels, speeds, job_speed=1.0, switch=None, row_switch=None):
     """n_in // B events of B frames, x[k B : (k + 1) B], each at its speed; the flush at the last speed; the trailing partial buffer
-    is dropped (soniclib.c:538-550).  Returns the stream."""
+    is dropped (soniclib.c:538-550).  Returns the stream.
+
+    `rows` beside it: the time map's rows as include/speedy_hip.h words them ("the output frames the time-scale stage has produced
+    when ring buffer k is about to be handed to it", then "the job's final count") -- frames_out immediately before each event's
+    write, and the final frames_out behind the flush: n_in // B + 1 rows, the final count alone for a job shorter than one buffer.
+    row_switch makes one mistake (ROW_SWITCHES): row_after_write counts behind the event's write, row_before_cut takes the last row
+    before the flush cuts the output."""
+    assert row_switch is None or row_switch in ROW_SWITCHES, row_switch
     B = rate // 100
     s = SpeedStream(rate, channels, switch)
     x = [int(v) for v in x]
     assert len(speeds) == len(x) // channels // B
+    rows = []
     for k, sp in enumerate(speeds):
+        if row_switch != "row_after_write":
+            rows.append(s.frames_out)
         s.write(x[k * B * channels:(k + 1) * B * channels], sp)
-    s.flush(speeds[-1] if len(speeds) else job_speed)
+        if row_switch == "row_after_write":
+            rows.append(s.frames_out)
+    s.flush(speeds[-1] if len(speeds) else job_speed, cut=row_switch != "row_before_cut")
+    rows.append(s.frames_out)
+    s.rows = rows
     return s
 
 
