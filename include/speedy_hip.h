@@ -135,12 +135,29 @@ int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, f
  * call refuses what spx_batch_run refuses, with the same messages, and a NULL map -- -1, spx_last_error, nothing enqueued.  The rows
  * of a job whose n_out comes back negative are unspecified.
  * COST: the whole batch runs on the GENERAL walk kernel (the speed-up kernels write no map yet), kernels in sequence on hip_stream,
- * as spx_batch_run_rate does: profiles/time_map.txt.  The plain call only.  OUT OF SCOPE: a map on the _rate, _float, _ahead,
- * _overlapped and _mixed* calls, on the pipeline object and on the streaming API (include/sonic2.h).
+ * as spx_batch_run_rate does: profiles/time_map.txt.  The plain call only.  OUT OF SCOPE: a map on the _ahead, _overlapped,
+ * _mixed* and _twopass calls, on the pipeline object and on the streaming API (include/sonic2.h).
+ *
+ * WITH PLAYBACK RATES, AND ON FLOAT SAMPLES: spx_batch_run_rate_map is spx_batch_run_rate, and spx_batch_run_float_map is
+ * spx_batch_run_float, with the same map beside it.  spx_plan_map_rows and the row layout are unchanged (the rate stage changes no
+ * row count); the rows count FINAL frames -- behind the rate stage, the unit of out, n_out and out_cap of these calls.  With
+ * (new, old) = (int)(sample rate / rates[i]) computed in float and the sample rate, halved together until both fit 14 bits, and
+ *   F(m) = 0 for m < 2, else ((m - 1) * new + old - 1) / old in int64     (the frames behind the rate stage after m frames of the speed stage)
+ *   nonlinear != 0, rates[i] != 1   M[k] = F(the row spx_batch_run_map writes for the same job), k < R; M[R] = n_out[i]
+ *   nonlinear == 0, rates[i] != 1   M[0] = n_out[i]
+ *   rates[i] == 1, or rates == NULL the rows of spx_batch_run_map, unchanged, in the same call as jobs with other rates
+ * Row k is what a streaming caller with sonicSetRate set sees in sonicSamplesAvailable at that hand-off (nothing read in between),
+ * and the rows never decrease, the last one included.  The rows of a job whose n_out comes back negative are unspecified.
+ * out, n_out and the taps are byte for byte spx_batch_run_rate's (spx_batch_run_float's) for the same table, and the workspace is
+ * spx_batch_workspace_bytes_rate (_float), unchanged: the rows are converted in place in `map`, by one small kernel behind the rate
+ * kernel.  With every rate 1 or rates == NULL spx_batch_run_rate_map IS spx_batch_run_map.  Refused with -1 and spx_last_error,
+ * nothing enqueued, the plan as it was: everything spx_batch_run_rate (_float) refuses, with its messages; a NULL map; more than
+ * 2^31 - 1 rows in one call.  The plain call only, kernels in sequence on hip_stream (profiles/time_map_rate.txt).
  *
  * spx_map_lookup converts positions on the device, asynchronous on hip_stream, in exact integer arithmetic (int64, floor division).
  *   jobs     HOST   the table the map was made with (n_in and nonlinear are read)
- *   map      DEVICE the rows spx_batch_run_map wrote
+ *   map      DEVICE the rows spx_batch_run_map wrote -- or spx_batch_run_rate_map / _float_map: the lookup interpolates whatever rows
+ *                   it is given, and on a map from those calls the output side (Y, forward's answers, inverse's queries) is in FINAL frames
  *   q_off    DEVICE int64[n_streams + 1]: stream i's queries are q[q_off[i] .. q_off[i + 1]) (an empty range is fine)
  *   q, r     DEVICE int64: positions in, positions out, same indices
  *   inverse  0: input frame -> output frame; otherwise output frame -> input frame
@@ -165,6 +182,12 @@ int spx_batch_run_map(spx_plan_t plan, const spx_stream_job* jobs, int n_streams
                       const spx_taps* taps, void* hip_stream);
 int spx_map_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int64_t* map, const int64_t* q_off,
                    const int64_t* q, int64_t* r, int inverse, void* hip_stream);
+int spx_batch_run_rate_map(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, const int16_t* in,
+                           int16_t* out, int64_t* n_out, int64_t* map, void* workspace, size_t workspace_bytes,
+                           const spx_taps* taps, void* hip_stream);
+int spx_batch_run_float_map(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n_streams, const float* in,
+                            float* out, int64_t* n_out, int64_t* map, void* workspace, size_t workspace_bytes,
+                            const spx_taps* taps, void* hip_stream);
 
 /* ---- TWO PASSES IN ONE CALL: every stream to a target length, or the linear control at the nonlinear duration ----
  * The reference's CLI has two two-pass drivers (speedy_wave.cc:424-462): --length runs a nonlinear pass at the requested speed,
@@ -601,6 +624,8 @@ int spx_debug_last_call_concurrent(void);
 double spx_timing_last_tension_ms(void);
 /* ... and of the rate kernel's (spx_batch_run_rate calls with a rate other than 1). */
 double spx_timing_last_rate_ms(void);
+/* ... and of the kernel that converts a time map's rows to final frames (spx_batch_run_rate_map / _float_map calls with a rate other than 1). */
+double spx_timing_last_map_rows_ms(void);
 
 /* Diagnostics: the number of pitch searches (libsonic's findPitchPeriod calls) each stream's walk has run since the stream started (a batch job starts it) -- the length of the stream's chain of dependent steps, which is what bounds a call with one stream per CU.
  *   workspace  DEVICE  the workspace that call ran with;  steps  HOST  int32[n_streams].  Waits for hip_stream first. */

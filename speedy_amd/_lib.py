@@ -51,6 +51,10 @@ SYMBOLS = {
                                     C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
     "spx_map_lookup": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int, C.c_void_p]),
+    "spx_batch_run_rate_map": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
+    "spx_batch_run_float_map": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
     "spx_batch_workspace_bytes_twopass": (C.c_size_t, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int]),
     "spx_plan_out_capacity_twopass": (C.c_int64, [C.c_void_p, C.c_int64, C.c_double, C.c_float]),
     "spx_batch_run_twopass": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p,
@@ -91,6 +95,7 @@ SYMBOLS = {
     "spx_timing_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "spx_timing_last_tension_ms": (C.c_double, []),
     "spx_timing_last_rate_ms": (C.c_double, []),
+    "spx_timing_last_map_rows_ms": (C.c_double, []),
     "spx_batch_kernel_names": (C.c_char_p, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "spx_batch_kernel_names_lean": (C.c_char_p, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "spx_debug_last_walk_form": (C.c_int, []),

@@ -49,15 +49,14 @@ class Batch:
     outputs are the final frames behind the rate stage; None: spx_batch_run, call for call as before.
     time_map: run() is spx_batch_run_map -- the same outputs, counts and taps, and a time map beside them: time_map(i) returns
     stream i's rows (the output frames produced when each 10 ms ring buffer of input is handed to the time-scale stage, then the
-    final count), lookup(i, positions) converts input frames to output frames (inverse=True: the other way) on the GPU.  The plain
-    call only: no rate, no run_ahead."""
+    final count), lookup(i, positions) converts input frames to output frames (inverse=True: the other way) on the GPU.  With
+    rate= as well, run() is spx_batch_run_rate_map and the rows, like the outputs, count final frames.  The plain call only: no
+    run_ahead."""
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
                  spectrogram_taps=False, rate=None, time_map=False):
         if time_map and not torch.cuda.is_available():
             raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
-        if time_map and rate is not None:
-            raise ValueError("a time map comes with the plain call only (spx_batch_run_map has no rate form)")
         self.plan = plan
         n = len(lengths)
         self.n = n
@@ -99,11 +98,7 @@ class Batch:
         self.d_nout = torch.zeros(n, dtype=torch.int64, device=dev)
         self.d_ws = torch.zeros(self._workspace_bytes(), dtype=torch.uint8, device=dev)
         if self.with_map:
-            # stream i's rows: d_map[map_offs[i] : map_offs[i + 1]] (spx_plan_map_rows per job, in job order)
-            self.map_offs = [0]
-            for i in range(n):
-                self.map_offs.append(self.map_offs[-1] + plan.L.spx_plan_map_rows(plan.h, int(self.lengths[i]), float(nlv[i])))
-            self.d_map = torch.zeros(self.map_offs[-1], dtype=torch.int64, device=dev)
+            self._alloc_map(nlv)
         self.taps = None
         if taps:
             T1 = max(1, fo)
@@ -117,6 +112,14 @@ class Batch:
                 self.t_norm = torch.zeros(T1 * plan.W, dtype=torch.float32, device=dev)
                 self.taps.spectrogram = self.t_spec.data_ptr()
                 self.taps.normalized = self.t_norm.data_ptr()
+
+    def _alloc_map(self, nonlinear):
+        """The time map's device buffer: stream i's rows are d_map[map_offs[i] : map_offs[i + 1]] (spx_plan_map_rows per job, in job order)."""
+        plan = self.plan
+        self.map_offs = [0]
+        for i in range(self.n):
+            self.map_offs.append(self.map_offs[-1] + plan.L.spx_plan_map_rows(plan.h, int(self.lengths[i]), float(nonlinear[i])))
+        self.d_map = torch.zeros(self.map_offs[-1], dtype=torch.int64, device=self.device)
 
     def _capacity(self, i, n_in, speed, nonlinear):
         """Output capacity of stream i in frames (a subclass with another capacity rule overrides this)."""
@@ -147,6 +150,14 @@ class Batch:
     def run(self, stream=None):
         """Enqueue the whole hot path (analysis + walk, and the rate stage of a batch with rates) on `stream` (torch stream or None)."""
         hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if self.rates is not None and self.with_map:
+            rc = self.plan.L.spx_batch_run_rate_map(self.plan.h, self.jobs, self._rates_ptr(), self.n, self.d_in.data_ptr(),
+                                                    self.d_out.data_ptr(), self.d_nout.data_ptr(), self.d_map.data_ptr(),
+                                                    self.d_ws.data_ptr(), self.d_ws.numel(),
+                                                    C.byref(self.taps) if self.taps is not None else None, hs)
+            if rc != 0:
+                raise RuntimeError("spx_batch_run_rate_map: " + self.plan.L.spx_last_error().decode())
+            return
         if self.rates is not None:
             rc = self.plan.L.spx_batch_run_rate(self.plan.h, self.jobs, self._rates_ptr(), self.n, self.d_in.data_ptr(),
                                                 self.d_out.data_ptr(), self.d_nout.data_ptr(), self.d_ws.data_ptr(),
@@ -236,7 +247,8 @@ class Batch:
     def time_map(self, i):
         """Stream i's time-map rows of the last run (host numpy int64): for a nonlinear stream row k < n_in // B is the number of
         output frames produced when input frames [k B, (k + 1) B) are handed to the time-scale stage, the last row is the final
-        count; a linear stream has the final count alone."""
+        count; a linear stream has the final count alone.  On a batch with rates (and on a FloatBatch) the rows count final frames,
+        behind the rate stage, as the outputs do."""
         if not self.with_map:
             raise RuntimeError("the batch was made without time_map=True")
         torch.cuda.synchronize(self.device)
@@ -356,15 +368,17 @@ class FloatBatch(Batch):
     already in device memory).  d_in / d_out are torch.float32 tensors packed like Batch's -- the same job table, offsets in
     float values -- and the int16 work in between is Batch's, bit for bit: the input is scaled per job as the reference scales it
     (nonlinear != 0: x * 32768.0 in double, else x * 32767.0f) and truncated, every output value is an int16 / 32767.0f.
-    rate: as Batch has it.  The plain call only: no run_ahead, no pack_outputs."""
+    rate: as Batch has it.  time_map: run() is spx_batch_run_float_map -- time_map(i), lookup_all and lookup as Batch has them, the
+    rows in final frames.  The plain call only: no run_ahead, no pack_outputs."""
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
-                 spectrogram_taps=False, rate=None):
+                 spectrogram_taps=False, rate=None, time_map=False):
         if not torch.cuda.is_available():
             raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
         self.plan = plan
         n = len(lengths)
         self.n = n
+        self.with_map = bool(time_map)
         self.rates = None
         if rate is not None:
             self.rates = np.ascontiguousarray(np.broadcast_to(np.asarray(rate, np.float32), (n,)))
@@ -402,6 +416,8 @@ class FloatBatch(Batch):
         if wsb == 0:
             raise RuntimeError("spx_batch_workspace_bytes_float: " + plan.L.spx_last_error().decode())
         self.d_ws = torch.zeros(wsb, dtype=torch.uint8, device=dev)
+        if self.with_map:
+            self._alloc_map(nlv)
         self.taps = None
         if taps:
             T1 = max(1, fo)
@@ -438,6 +454,14 @@ class FloatBatch(Batch):
     def run(self, stream=None):
         """Enqueue input conversion, the int16 call and output conversion on `stream` (torch stream or None)."""
         hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if self.with_map:
+            rc = self.plan.L.spx_batch_run_float_map(self.plan.h, self.jobs, self._rates_ptr(), self.n, self.d_in.data_ptr(),
+                                                     self.d_out.data_ptr(), self.d_nout.data_ptr(), self.d_map.data_ptr(),
+                                                     self.d_ws.data_ptr(), self.d_ws.numel(),
+                                                     C.byref(self.taps) if self.taps is not None else None, hs)
+            if rc != 0:
+                raise RuntimeError("spx_batch_run_float_map: " + self.plan.L.spx_last_error().decode())
+            return
         rc = self.plan.L.spx_batch_run_float(self.plan.h, self.jobs, self._rates_ptr(), self.n, self.d_in.data_ptr(),
                                              self.d_out.data_ptr(), self.d_nout.data_ptr(), self.d_ws.data_ptr(),
                                              self.d_ws.numel(), C.byref(self.taps) if self.taps is not None else None, hs)

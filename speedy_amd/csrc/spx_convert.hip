@@ -266,8 +266,11 @@ size_t spx_batch_workspace_bytes_float(spx_plan_t plan, const spx_stream_job* jo
   return FL.total;
 }
 
-int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const float* in, float* out,
-                        int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
+}  // extern "C"
+
+// spx_batch_run_float, and (with_map) spx_batch_run_float_map: the same layers, the map handed through to the int16 call.
+static int run_float(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const float* in, float* out,
+                     int64_t* n_out, bool with_map, int64_t* map, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
   // ---- everything that is refused is refused before the first launch ----
   if (!plan || !jobs || n <= 0 || !in || !out || !n_out || !ws) return fail(-1, "spx_batch_run_float: bad arguments (a null pointer or no streams)");
   if ((reinterpret_cast<uintptr_t>(in) & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
@@ -276,6 +279,12 @@ int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float
   FloatLayout FL;
   if (float_layout(plan, jobs, rates, n, FL)) return -1;   // a job or a rate that is refused
   if (ws_bytes < FL.total) return fail(-1, "spx_batch_run_float: workspace too small (spx_batch_workspace_bytes_float)");
+  if (with_map) {   // what the int16 call with a map refuses on top of that -- asked here, ahead of the input conversion's launch
+    if (!map) return fail(-1, "spx_batch_run_float_map: map is NULL");
+    int64_t rows = 0;
+    for (int i = 0; i < n; i++) rows += spx_map_rows(plan->dev, jobs[i].n_in, jobs[i].nonlinear != 0.0f);
+    if (rows > 0x7fffffff) return fail(-1, "spx_batch_run_float_map: more than 2^31 - 1 map rows in one call");
+  }
   hipStream_t st = static_cast<hipStream_t>(hs);
   unsigned char* w = static_cast<unsigned char*>(ws);
   SpxConvJob* d_tab = reinterpret_cast<SpxConvJob*>(w + FL.off_table);
@@ -294,10 +303,21 @@ int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float
 
   // ---- input conversion | the int16 call on the stagings | output conversion, all on hip_stream ----
   conv_launch_in(d_tab, n, max_in, in, st_in, st);
-  const int rc = spx_batch_run_rate(plan, jobs, rates, n, st_in, st_out, n_out, ws, FL.base, taps, hs);
+  const int rc = with_map ? spx_batch_run_rate_map(plan, jobs, rates, n, st_in, st_out, n_out, map, ws, FL.base, taps, hs)
+                          : spx_batch_run_rate(plan, jobs, rates, n, st_in, st_out, n_out, ws, FL.base, taps, hs);
   if (rc) return rc;
   conv_launch_out(d_tab, n, max_out, n_out, st_out, out, st);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+extern "C" {
+int spx_batch_run_float(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const float* in, float* out,
+                        int64_t* n_out, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
+  return run_float(plan, jobs, rates, n, in, out, n_out, false, nullptr, ws, ws_bytes, taps, hs);
+}
+int spx_batch_run_float_map(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const float* in, float* out,
+                            int64_t* n_out, int64_t* map, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
+  return run_float(plan, jobs, rates, n, in, out, n_out, true, map, ws, ws_bytes, taps, hs);
 }
 }  // extern "C"

@@ -151,7 +151,7 @@ struct spx_plan {
 };
 
 // ---- process-wide state (spx_engine.hip) ----
-struct EvPair { hipEvent_t a, b; int kind; };  // kind 0 = analysis launch, 1 = walk launch, 2 = tension launch, 3 = rate launch (spx_batch_run_rate)
+struct EvPair { hipEvent_t a, b; int kind; };  // kind 0 = analysis launch, 1 = walk launch, 2 = tension launch, 3 = rate launch (spx_batch_run_rate), 4 = the map's rows conversion (spx_batch_run_rate_map)
 extern std::atomic<bool> g_timing;
 extern std::atomic<int> g_last_concurrent;   // spx_debug_last_call_concurrent (2 = pipelined with the previous call)
 extern std::atomic<int> g_concurrent;        // spx_set_concurrent
@@ -244,6 +244,11 @@ struct SpxRateCall {
   const int16_t* tsm_base = nullptr;                 // the base SpxRateJob::tsm_off counts from
   int max_blocks = 1;
 };
+// spx_map.hip: the rows of a rate call with a time map (spx_batch_run_rate_map), from speed-stage frames to final frames in place,
+// behind the rate kernel.  jobs: DEVICE, the call's SpxRateJob records; streams: DEVICE, the SpxStreamDev records of the call's last
+// time chunk; n_out: DEVICE, the final counts; max_rows: the longest stream's row count.
+void spx_launch_map_rate_rows(const SpxRateJob* jobs, const SpxStreamDev* streams, int n_streams, int B, int64_t max_rows,
+                              const int64_t* n_out, int64_t* map, hipStream_t hs);
 // The second pass of a two-pass call (spx_batch_run_twopass, spx_twopass.hip): the speeds of the job table are not known on the host
 // -- a retarget kernel behind the staging kernel works them out from the first pass's counts (spx_twopass.h) and patches them into
 // the staged SpxStreamDev records.  Kernels in sequence on the caller's stream; the speed in the host table is a placeholder that

@@ -565,7 +565,8 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   std::vector<int> tiles;
   build_streams(d, jobs, n, nch, sv, tiles, opt.rate, opt.map != nullptr);
   if (opt.rate && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_rate: internal: not a plain call in sequence");
-  if (opt.map && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force || opt.rate)) return fail(-1, "spx_batch_run_map: internal: not a plain call in sequence");
+  // (a rate call with a map: both conditions hold, the same kernel serves both -- spx_batch_run_rate_map)
+  if (opt.map && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_map: internal: not a plain call in sequence");
   if (retarget && (concurrent || ahead || chunk_ahead || !do_w || force || opt.rate || opt.map || opt.ahead_req || opt.detached))
     return fail(-1, "spx_batch_run_twopass: internal: not a plain call in sequence");
   if (opt.map && (R.walk.fast_kernel || spx_walk_config(d, {.n_streams = n, .max_channels = maxC}).mode != 0))
@@ -725,6 +726,12 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
       if (opt.rate && c == nch - 1) {   // the rate stage: TSM buffer -> the caller's out, final counts -> n_out
         SpxTimed tm(timed, 3, stw);
         spx_launch_rate_batch(opt.rate->d_table, n, opt.rate->max_blocks, states, opt.rate->d_tsm_n, opt.rate->tsm_base, out, n_out, stw);
+      }
+      if (opt.rate && opt.map && c == nch - 1) {   // the map's rows, written in speed-stage frames by every chunk's walk kernel: to final frames
+        SpxTimed tm(timed, 4, stw);
+        int64_t max_rows = 1;
+        for (int i = 0; i < n; i++) max_rows = std::max(max_rows, spx_map_rows(d, jobs[i].n_in, jobs[i].nonlinear != 0.0f));
+        spx_launch_map_rate_rows(opt.rate->d_table, dj, n, d.B, max_rows, n_out, opt.map, stw);
       }
       if (M.ahead_forced && force->started_out) *force->started_out = d_ready + n;
       if (c == nch - 1 && !force) {
@@ -1052,6 +1059,26 @@ int spx_batch_run_rate(spx_plan_t plan, const spx_stream_job* jobs, const float*
   if (!any) return run_split(c, SpxCallOpts());   // spx_batch_run
   SpxCallOpts o;
   o.rate = &RC;
+  return run_impl(c, o);
+}
+// spx_batch_run_rate that also writes the time map, in FINAL frames: the walk kernel's map instantiation writes speed-stage rows,
+// the rate kernel the final counts, and the rows conversion (spx_map.hip) follows it.  Refuses what spx_batch_run_rate refuses,
+// with its messages, before the map is looked at.
+int spx_batch_run_rate_map(spx_plan_t plan, const spx_stream_job* jobs, const float* rates, int n, const int16_t* in, int16_t* out,
+                           int64_t* n_out, int64_t* map, void* ws, size_t ws_bytes, const spx_taps* taps, void* hs) {
+  if (!plan || !jobs || n <= 0) return fail(-1, "spx_batch: bad arguments");
+  const SpxCall c = {plan, jobs, n, in, out, n_out, ws, ws_bytes, taps, hs};
+  SpxRateCall RC;
+  bool any = false;
+  if (rate_call_build(c, rates, RC, &any)) return -1;
+  if (!any) return spx_batch_run_map(plan, jobs, n, in, out, n_out, map, ws, ws_bytes, taps, hs);   // every rate 1: that call
+  if (!map) return fail(-1, "spx_batch_run_rate_map: map is NULL");
+  int64_t rows = 0;
+  for (int i = 0; i < n; i++) rows += spx_map_rows(plan->dev, jobs[i].n_in, jobs[i].nonlinear != 0.0f);
+  if (rows > 0x7fffffff) return fail(-1, "spx_batch_run_rate_map: more than 2^31 - 1 map rows in one call");
+  SpxCallOpts o;
+  o.rate = &RC;
+  o.map = map;
   return run_impl(c, o);
 }
 }  // extern "C"

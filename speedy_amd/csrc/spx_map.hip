@@ -5,6 +5,8 @@
 // the number of frames the time-scale stage has produced when ring buffer k -- input frames [kB, (k+1)B) -- is about to be handed
 // to it, the last row is the job's final count; a linear job has the final count alone.  spx_batch_run_map is spx_batch_run with
 // SpxCallOpts::map set (run_impl: the whole batch on the general kernel, kernels in sequence on the caller's stream).
+// spx_batch_run_rate_map (spx_engine.hip) is spx_batch_run_rate with the same option: the rows conversion kernel below follows the
+// rate kernel and turns the speed-stage rows into final frames.
 //
 // The lookup kernel interpolates between the nodes in exact int64 arithmetic:
 //   R = complete ring buffers of a nonlinear job (0 for a linear one)
@@ -70,6 +72,48 @@ spx_map_lookup_kernel(const SpxMapStream* __restrict__ streams, int stream0, int
       }
     }
     r[i] = ans;
+  }
+}
+
+// Rows of a call with playback rates (spx_batch_run_rate_map), converted in place behind the rate kernel: the walk kernel has written
+// SPEED-STAGE rows (its flush untruncated where a rate stage follows), the caller is owed FINAL frames.  The rate stage is a closed
+// form (spx_rate_batch.hip): after m frames of the speed stage F(m) = 0 for m < 2, else ceil((m - 1) * new / old) final frames
+// exist.  Rows 0 .. R-1 become F(row); the last row (a linear job's only one) is the final count the rate kernel left in n_out.
+// A stream with rate 1 (bypass) keeps the rows spx_batch_run_map gives it.
+// Grid over (row block, stream) as the lookup kernel's; the stream's SpxRateJob record and the last time chunk's SpxStreamDev
+// record (map_row, the whole n_in) are the ones the call has staged in the workspace.  One 8-byte load and one 8-byte store per
+// row.  A negative row (INT64_MIN included: a job whose result is unspecified) takes the m < 2 branch: nothing is indexed by a
+// row, and the one divisor is the record's old_rate (>= 1: rate_ratio).
+__global__ void __launch_bounds__(SPX_MAP_THREADS)
+spx_map_rate_rows_kernel(const SpxRateJob* __restrict__ jobs, const SpxStreamDev* __restrict__ streams, int stream0, int B,
+                         const int64_t* __restrict__ n_out, int64_t* __restrict__ map) {
+  const int s = stream0 + (int)blockIdx.y;
+  const SpxRateJob J = jobs[s];
+  if (J.bypass) return;
+  const int64_t R = streams[s].nonlinear != 0.0f ? streams[s].n_in / B : 0;
+  int64_t* __restrict__ rows = map + streams[s].map_row;
+  const int64_t newR = J.new_rate, oldR = J.old_rate;
+  const int64_t stride = (int64_t)gridDim.x * SPX_MAP_THREADS;
+  for (int64_t k = (int64_t)blockIdx.x * SPX_MAP_THREADS + threadIdx.x; k <= R; k += stride) {
+    if (k == R) {
+      rows[k] = n_out[s];
+    } else {
+      const int64_t m = rows[k];
+      rows[k] = m >= 2 ? ((m - 1) * newR + oldR - 1) / oldR : 0;
+    }
+  }
+}
+
+// streams: DEVICE, the call's LAST time chunk's records; max_rows: the longest stream's row count (the grid's width: a thread
+// strides over what 64 blocks do not cover).
+void spx_launch_map_rate_rows(const SpxRateJob* jobs, const SpxStreamDev* streams, int n_streams, int B, int64_t max_rows,
+                              const int64_t* n_out, int64_t* map, hipStream_t hs) {
+  int64_t gx = (max_rows + SPX_MAP_THREADS - 1) / SPX_MAP_THREADS;
+  gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
+  for (int s0 = 0; s0 < n_streams; s0 += 65535) {   // (the grid's second dimension holds 65 535)
+    const int m = n_streams - s0 < 65535 ? n_streams - s0 : 65535;
+    hipLaunchKernelGGL(spx_map_rate_rows_kernel, dim3((unsigned)gx, (unsigned)m), dim3(SPX_MAP_THREADS), 0, hs, jobs, streams, s0, B,
+                       n_out, map);
   }
 }
 

@@ -9,7 +9,15 @@ inputs).
                                          speedy_amd/lib/ab/libspeedy_hip_<NAME>.so for every NAME (tools/build_variant.sh's place)
   python tools/time_map_time.py map      this build: spx_batch_run_map on the same table (and spx_batch_run beside it, same
                                          process), its kernels one by one, and spx_map_lookup for 256 x 1000 queries, both
-                                         directions; the outputs of the two calls are compared byte for byte"""
+                                         directions; the outputs of the two calls are compared byte for byte
+
+Times behind profiles/time_map_rate.txt: the same table, every playback rate 1.25.
+  python tools/time_map_time.py rate     spx_batch_run_rate, ms per call -- one line; SPEEDY_HIP_LIB selects the build
+  python tools/time_map_time.py ab-rate parent parent2
+                                         `rate` in a fresh process per build, two rounds interleaved, as `ab` does for `run`
+  python tools/time_map_time.py ratemap  this build: spx_batch_run_rate and spx_batch_run_rate_map in one process, the outputs
+                                         compared byte for byte, and the map call's kernels one by one -- the rows conversion
+                                         kernel (spx_timing_last_map_rows_ms) alone among them"""
 import ctypes as C
 import os
 import statistics
@@ -56,14 +64,61 @@ def run(xs):
     plan.close()
 
 
-def ab(names):
+RATE = 1.25
+
+
+def run_rate(xs):
+    from speedy_amd.batch import Batch, Plan
+    plan = Plan(RATE_HZ, False)
+    n = SECONDS * RATE_HZ
+    p = Batch(plan, [n] * len(xs), 1, SPEED, NL, 0.0, rate=RATE)
+    p.upload(xs)
+    line("spx_batch_run_rate at %g, 30 calls back to back after 5" % RATE, timed(p.run))
+    plan.close()
+
+
+def with_rate_map(xs):
+    import torch
+    from speedy_amd.batch import Batch, Plan
+    plan = Plan(RATE_HZ, False)
+    L = plan.L
+    n = SECONDS * RATE_HZ
+    p = Batch(plan, [n] * len(xs), 1, SPEED, NL, 0.0, rate=RATE)
+    p.upload(xs)
+    m = Batch(plan, [n] * len(xs), 1, SPEED, NL, 0.0, rate=RATE, time_map=True)
+    m.upload(xs)
+    for r in (1, 2):   # interleaved: the spread between the rounds is the run-to-run spread of this process
+        line("round %d  spx_batch_run_rate at %g" % (r, RATE), timed(p.run))
+        line("round %d  spx_batch_run_rate_map at %g" % (r, RATE), timed(m.run))
+    torch.cuda.synchronize()
+    same = bool((m.d_nout == p.d_nout).all()) and bool((m.d_out == p.d_out).all())
+    rows = m.d_map.cpu().numpy()
+    print("out and n_out of the two calls byte-equal: %s; map rows %d (%.2f MB); last rows equal n_out: %s"
+          % (same, rows.size, rows.size * 8 / 1e6, bool((rows[np.asarray(m.map_offs[1:]) - 1] == m.d_nout.cpu().numpy()).all())))
+    L.spx_set_timing(1)
+    ka, kw, kt, kr, km = [], [], [], [], []
+    for i in range(25):
+        m.run()
+        a, w, c = C.c_double(0), C.c_double(0), C.c_int(0)
+        assert L.spx_timing_collect(C.byref(a), C.byref(w), C.byref(c)) == 0 and c.value == 1
+        if i >= 5:
+            ka.append(a.value); kw.append(w.value); kt.append(L.spx_timing_last_tension_ms())
+            kr.append(L.spx_timing_last_rate_ms()); km.append(L.spx_timing_last_map_rows_ms())
+    L.spx_set_timing(0)
+    print("rate map call's kernels, median ms: analysis %.3f tension %.3f walk (general kernel, map instantiation) %.3f rate %.3f"
+          % (statistics.median(ka), statistics.median(kt), statistics.median(kw), statistics.median(kr)))
+    line("rows conversion kernel alone (HIP events around its launch, %d rows)" % rows.size, km)
+    plan.close()
+
+
+def ab(names, mode="run"):
     for r in (1, 2):
         for v in ["shipped"] + names:
             env = dict(os.environ)
             env.pop("SPEEDY_HIP_LIB", None)
             if v != "shipped":
                 env["SPEEDY_HIP_LIB"] = os.path.join(ROOT, "speedy_amd", "lib", "ab", "libspeedy_hip_%s.so" % v)
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "run"], env=env, capture_output=True, text=True, timeout=300)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), mode], env=env, capture_output=True, text=True, timeout=300)
             if out.returncode != 0:
                 sys.exit("round %d, %s: exit %d\n%s" % (r, v, out.returncode, out.stderr[-2000:]))
             print("round %d  %-8s %s" % (r, v, out.stdout.strip().splitlines()[-1]), flush=True)
@@ -115,11 +170,11 @@ def with_map(xs):
 
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else ""
-    if mode not in ("run", "ab", "map"):
+    if mode not in ("run", "ab", "map", "rate", "ab-rate", "ratemap"):
         sys.exit(__doc__)
-    if mode == "ab":
-        ab(sys.argv[2:])
+    if mode in ("ab", "ab-rate"):
+        ab(sys.argv[2:], "run" if mode == "ab" else "rate")
         sys.exit(0)
     import torch
     assert torch.cuda.is_available(), "needs an MI355X"
-    (run if mode == "run" else with_map)(streams())
+    {"run": run, "map": with_map, "rate": run_rate, "ratemap": with_rate_map}[mode](streams())
