@@ -189,6 +189,68 @@ int spx_batch_run_float_map(spx_plan_t plan, const spx_stream_job* jobs, const f
                             float* out, int64_t* n_out, int64_t* map, void* workspace, size_t workspace_bytes,
                             const spx_taps* taps, void* hip_stream);
 
+/* ---- EDIT LIST: the copies and cross-fades a job performed, and their replay on other tracks ----
+ * Every output frame of a job is either a run of input frames copied through or a cross-fade of two runs.  spx_batch_run_edits is
+ * spx_batch_run that also writes that list down, and spx_edit_replay applies a list to any other track of the same length -- a clean
+ * recording beside the noisy one, stems, a dubbed language, a per-sample mask -- so that speed and pitch are decided on ONE track
+ * and every companion is cut in exactly the same places.  Decide once, render many times: each further track costs a pass over its
+ * bytes, not another walk (profiles/edit_list.txt).
+ *
+ * A record (spx_edit_op, 16 bytes, n >= 1):
+ *   b <  0   a copy:        output frame out_at + t = source frame a + t, t < n
+ *   b >= 0   a cross-fade:  per channel, output frame out_at + t = (y[a + t] * (n - t) + y[b + t] * t) / n, truncated toward zero
+ *            (a: the ramp going down, b: the ramp coming up)
+ * A source frame at or behind L reads as 0: L = n_in for a linear job, (n_in / B) * B for a nonlinear one (B = spx_plan_frame_step:
+ * the trailing partial ring buffer is dropped, and the flush pads with zeros).  Records come in the order the time-scale stage emits
+ * them -- a speed-up step is one cross-fade; a slow-down step a copy and then a cross-fade (a step that fails leaves its copy); every
+ * piece of a pending copy-through, at most spx_plan_max_required frames, a copy; a write at unity speed one copy of everything
+ * pending -- and are contiguous: ops[0].out_at = 0, ops[k + 1].out_at = ops[k].out_at + ops[k].n.  The flush's cut removes no
+ * record: frames at or behind n_out are not part of the output.  Every position fits int32 (n_in < 2^30 plus padding; the walk
+ * kernel counts at most 2^31 - 1 output frames).
+ *
+ * spx_batch_run_edits
+ *   ops      DEVICE, aligned to 16 bytes; stream i's records start at the sum of ops_cap of the streams in front of it
+ *   ops_cap  HOST   int64[n_streams], records per stream (spx_plan_edit_ops, or any value >= 0)
+ *   n_ops    DEVICE int64[n_streams]: the number of records of each job.  A job that has more than ops_cap[i] comes back as MINUS the
+ *            number it has: the kernel keeps counting and stops storing, nothing is written behind the stream's region, out and
+ *            n_out are unaffected -- call again with that capacity.  Where n_out[i] is negative the stream's records are unspecified.
+ * out, n_out and the taps are byte for byte spx_batch_run's for the same table; the workspace is spx_batch_workspace_bytes.  Refused
+ * with -1 and spx_last_error, nothing enqueued, the plan as it was: everything spx_batch_run refuses, with its messages; a NULL or
+ * misaligned ops, a NULL ops_cap or n_ops; a negative capacity; more than 2^31 - 1 records of capacity in one call.
+ * COST: as spx_batch_run_map -- the whole batch on the GENERAL walk kernel, kernels in sequence on hip_stream -- plus one 16-byte
+ * store per record.  The plain call only.  OUT OF SCOPE: an edit list on the _rate, _float, _map, _twopass, _ahead, _overlapped and
+ * _mixed* calls, on the pipeline object and on the streaming API; float tracks; a sample-exact position lookup over the records
+ * (spx_map_lookup answers to 10 ms; the list makes the exact answer possible -- the follow-up).
+ *
+ * spx_plan_edit_ops returns a capacity that holds every record of a job NONE OF WHOSE STEPS FAILS (-1 for values spx_batch_run
+ * refuses).  A step fails when its cross-fade would have no frame: with minPeriod = sample rate / 400, a linear job with
+ * 1 / minPeriod <= speed <= minPeriod has no failed step, and a nonlinear job has none while every speed of its speed tap lies in
+ * that range -- the library cannot know those speeds before the call, so for a nonlinear job the value is a capacity that holds
+ * unless the tension drives an event's speed outside the range.  A job whose steps fail processes its pending input again at the next
+ * event (the stage consumes nothing on a failure), so no bound linear in the length covers it: the negative count in n_ops is the
+ * answer there.
+ *
+ * spx_edit_replay runs asynchronously on hip_stream: for each stream, out_y[o], o < n_out[i], is the value of the record that covers
+ * o, computed on the track y -- any channel count, n_in frames.  Replaying a job's list on the job's own input gives the job's out,
+ * byte for byte.
+ *   jobs     HOST   the table the list was made with (n_in, nonlinear and out_cap are read)
+ *   ops, ops_cap, n_ops, n_out   as spx_batch_run_edits took and left them (n_ops, n_out: DEVICE -- nothing comes back to the host)
+ *   tracks   HOST   one per stream: in_off / out_off in int16 values from y_in / y_out, channels in 1 .. 65535; out_off addresses
+ *            jobs[i].out_cap frames of `channels` values
+ *   y_in     DEVICE read only below L frames per stream: no padding behind the last track is needed (unlike spx_batch_run's `in`)
+ *   y_out    DEVICE a stream with n_out[i] <= 0 or n_ops[i] < 0 gets nothing written; no other gets more than n_out[i] frames
+ * Refused with -1 and spx_last_error before anything is enqueued: a NULL pointer; a track with channels < 1 (or above 65535) or a
+ * negative offset; a misaligned ops; a table spx_batch_run refuses. */
+typedef struct { int32_t out_at, a, b, n; } spx_edit_op;
+typedef struct { int64_t in_off, out_off; int32_t channels, reserved; } spx_edit_track;
+int64_t spx_plan_edit_ops(spx_plan_t plan, int64_t n_in, float speed, float nonlinear);
+int spx_batch_run_edits(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const int16_t* in, int16_t* out, int64_t* n_out,
+                        spx_edit_op* ops, const int64_t* ops_cap, int64_t* n_ops, void* workspace, size_t workspace_bytes,
+                        const spx_taps* taps, void* hip_stream);
+int spx_edit_replay(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const spx_edit_op* ops, const int64_t* ops_cap,
+                    const int64_t* n_ops, const int64_t* n_out, const spx_edit_track* tracks, const int16_t* y_in, int16_t* y_out,
+                    void* hip_stream);
+
 /* ---- TWO PASSES IN ONE CALL: every stream to a target length, or the linear control at the nonlinear duration ----
  * The reference's CLI has two two-pass drivers (speedy_wave.cc:424-462): --length runs a nonlinear pass at the requested speed,
  * measures what came out and runs the final pass at want * (want / achieved), so that the output lands on the requested duration;
@@ -555,6 +617,8 @@ int spx_debug_last_call_chunks(void);
 /* Diagnostics: the query blocks per stream of the last spx_map_lookup of this process (4 .. 1 024); *launches (may be NULL) = the
  * kernel launches it took (one per 65 535 streams); 0 before the first call. */
 int spx_debug_last_lookup_grid(int* launches);
+/* ... and the output blocks per stream of the last spx_edit_replay (4 096 int16 values each), with its launches. */
+int spx_debug_last_replay_grid(int* launches);
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls);
 /* "analysis;tension;walk": the kernels (template arguments included, as a profiler prints them) that serve a batch of
  * n_streams streams with at most max_channels channels; speedup_only = every job has speed > 1. */

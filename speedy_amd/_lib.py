@@ -22,6 +22,10 @@ class Taps(C.Structure):  # spx_taps
                 ("spectrogram", C.c_void_p), ("normalized", C.c_void_p)]
 
 
+class EditTrack(C.Structure):  # spx_edit_track
+    _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("channels", C.c_int32), ("reserved", C.c_int32)]
+
+
 TENSION_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float)
 FEATURES_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, c_float_p)
 
@@ -55,6 +59,11 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
     "spx_batch_run_float_map": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), c_float_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
+    "spx_plan_edit_ops": (C.c_int64, [C.c_void_p, C.c_int64, C.c_float, C.c_float]),
+    "spx_batch_run_edits": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      c_int64_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
+    "spx_edit_replay": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(EditTrack), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spx_batch_workspace_bytes_twopass": (C.c_size_t, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int]),
     "spx_plan_out_capacity_twopass": (C.c_int64, [C.c_void_p, C.c_int64, C.c_double, C.c_float]),
     "spx_batch_run_twopass": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p,
@@ -92,6 +101,7 @@ SYMBOLS = {
     "spx_debug_last_tension_form": (C.c_int, []),
     "spx_debug_last_call_chunks": (C.c_int, []),
     "spx_debug_last_lookup_grid": (C.c_int, [C.POINTER(C.c_int)]),
+    "spx_debug_last_replay_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_timing_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "spx_timing_last_tension_ms": (C.c_double, []),
     "spx_timing_last_rate_ms": (C.c_double, []),

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import StreamJob, Taps, lib
+from ._lib import EditTrack, StreamJob, Taps, lib
 
 
 class Plan:
@@ -51,16 +51,23 @@ class Batch:
     stream i's rows (the output frames produced when each 10 ms ring buffer of input is handed to the time-scale stage, then the
     final count), lookup(i, positions) converts input frames to output frames (inverse=True: the other way) on the GPU.  With
     rate= as well, run() is spx_batch_run_rate_map and the rows, like the outputs, count final frames.  The plain call only: no
-    run_ahead."""
+    run_ahead.
+    edits: run() is spx_batch_run_edits -- the same outputs, counts and taps, and the jobs' edit lists beside them: edits(i) returns
+    stream i's records (out_at, a, b, n), replay(tracks, channels) applies the lists to companion tracks of the same lengths on the
+    GPU (spx_edit_replay).  The capacities are spx_plan_edit_ops' (ops_caps: one value or one per stream instead); not together
+    with rate or time_map.  The plain call only."""
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
-                 spectrogram_taps=False, rate=None, time_map=False):
-        if time_map and not torch.cuda.is_available():
+                 spectrogram_taps=False, rate=None, time_map=False, edits=False, ops_caps=None):
+        if edits and (rate is not None or time_map):
+            raise ValueError("edits=True goes with neither rate nor time_map (spx_batch_run_edits is the plain call's)")
+        if (time_map or edits) and not torch.cuda.is_available():
             raise RuntimeError("speedy_amd needs a HIP device; there is no CPU path")
         self.plan = plan
         n = len(lengths)
         self.n = n
         self.with_map = bool(time_map)
+        self.with_edits = bool(edits)
         self.rates = None
         if rate is not None:
             if not torch.cuda.is_available():
@@ -99,6 +106,8 @@ class Batch:
         self.d_ws = torch.zeros(self._workspace_bytes(), dtype=torch.uint8, device=dev)
         if self.with_map:
             self._alloc_map(nlv)
+        if self.with_edits:
+            self._alloc_edits(sp, nlv, ops_caps)
         self.taps = None
         if taps:
             T1 = max(1, fo)
@@ -120,6 +129,23 @@ class Batch:
         for i in range(self.n):
             self.map_offs.append(self.map_offs[-1] + plan.L.spx_plan_map_rows(plan.h, int(self.lengths[i]), float(nonlinear[i])))
         self.d_map = torch.zeros(self.map_offs[-1], dtype=torch.int64, device=self.device)
+
+    def _alloc_edits(self, speed, nonlinear, ops_caps):
+        """The edit list's device buffers: stream i's records are d_ops[op_offs[i] : op_offs[i] + n_ops[i]] (rows of four int32)."""
+        plan = self.plan
+        if ops_caps is None:
+            caps = [plan.L.spx_plan_edit_ops(plan.h, int(self.lengths[i]), float(speed[i]), float(nonlinear[i])) for i in range(self.n)]
+            if min(caps) < 0:
+                raise RuntimeError("spx_plan_edit_ops: " + plan.L.spx_last_error().decode())
+        else:
+            caps = [int(v) for v in np.broadcast_to(np.asarray(ops_caps, np.int64), (self.n,))]
+        self.ops_caps = np.ascontiguousarray(caps, np.int64)
+        self.op_offs = [0] + [int(v) for v in np.cumsum(self.ops_caps)]
+        self.d_ops = torch.zeros((max(1, self.op_offs[-1]), 4), dtype=torch.int32, device=self.device)
+        self.d_nops = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+
+    def _ops_cap_ptr(self):
+        return self.ops_caps.ctypes.data_as(C.POINTER(C.c_int64))
 
     def _capacity(self, i, n_in, speed, nonlinear):
         """Output capacity of stream i in frames (a subclass with another capacity rule overrides this)."""
@@ -172,6 +198,14 @@ class Batch:
             if rc != 0:
                 raise RuntimeError("spx_batch_run_map: " + self.plan.L.spx_last_error().decode())
             return
+        if self.with_edits:
+            rc = self.plan.L.spx_batch_run_edits(self.plan.h, self.jobs, self.n, self.d_in.data_ptr(), self.d_out.data_ptr(),
+                                                 self.d_nout.data_ptr(), self.d_ops.data_ptr(), self._ops_cap_ptr(),
+                                                 self.d_nops.data_ptr(), self.d_ws.data_ptr(), self.d_ws.numel(),
+                                                 C.byref(self.taps) if self.taps is not None else None, hs)
+            if rc != 0:
+                raise RuntimeError("spx_batch_run_edits: " + self.plan.L.spx_last_error().decode())
+            return
         rc = self.plan.L.spx_batch_run(self.plan.h, self.jobs, self.n, self.d_in.data_ptr(), self.d_out.data_ptr(),
                                        self.d_nout.data_ptr(), self.d_ws.data_ptr(), self.d_ws.numel(),
                                        C.byref(self.taps) if self.taps is not None else None, hs)
@@ -187,6 +221,8 @@ class Batch:
             raise RuntimeError("a batch with rates runs through the plain call only (spx_batch_run_rate)")
         if self.with_map:
             raise RuntimeError("a batch with a time map runs through the plain call only (spx_batch_run_map)")
+        if self.with_edits:
+            raise RuntimeError("a batch with an edit list runs through the plain call only (spx_batch_run_edits)")
         hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
         if overlap:
             assert in_ready is None
@@ -281,6 +317,52 @@ class Batch:
         """Stream i's positions through the time map: input frames to output frames (inverse=True: the other way)."""
         empty = np.zeros(0, np.int64)
         return self.lookup_all([positions if k == i else empty for k in range(self.n)], inverse)[i]
+
+    def op_counts(self):
+        """Records per stream of the last run (host numpy int64; minus the count where the capacity was too small); synchronises."""
+        if not self.with_edits:
+            raise RuntimeError("the batch was made without edits=True")
+        torch.cuda.synchronize(self.device)
+        return self.d_nops.cpu().numpy().copy()
+
+    def edits(self, i):
+        """Stream i's edit list of the last run: an (n_ops, 4) int32 array of (out_at, a, b, n) -- b < 0: n frames copied from input
+        frame a to output frame out_at; b >= 0: n frames of cross-fade from the run at a (fading out) to the run at b (fading in)."""
+        k = int(self.op_counts()[i])
+        if k < 0:
+            raise RuntimeError("stream %d has %d records, its capacity holds %d" % (i, -k, int(self.ops_caps[i])))
+        return self.d_ops[self.op_offs[i]:self.op_offs[i] + k].cpu().numpy().copy()
+
+    def replay(self, tracks, channels, stream=None):
+        """spx_edit_replay over the whole batch: tracks[i] = a companion of stream i (int16, interleaved, the stream's length in
+        frames), channels = its channel count (one value or one per stream, any count).  Returns the replayed tracks (host numpy
+        int16), trimmed to the streams' output lengths."""
+        if not self.with_edits:
+            raise RuntimeError("the batch was made without edits=True")
+        assert len(tracks) == self.n
+        ch = np.broadcast_to(np.asarray(channels, np.int32), (self.n,))
+        tr = (EditTrack * self.n)()
+        in_off = out_off = 0
+        for i in range(self.n):
+            tr[i].in_off, tr[i].out_off, tr[i].channels, tr[i].reserved = in_off, out_off, int(ch[i]), 0
+            in_off += int(self.lengths[i]) * int(ch[i])
+            out_off += int(self.out_caps[i]) * int(ch[i])
+        host = np.zeros(max(1, in_off), np.int16)
+        for i, y in enumerate(tracks):
+            y = np.ascontiguousarray(y, np.int16).ravel()
+            assert y.size == int(self.lengths[i]) * int(ch[i])
+            host[tr[i].in_off:tr[i].in_off + y.size] = y
+        d_y = torch.from_numpy(host).to(self.device)
+        d_yout = torch.zeros(max(1, out_off), dtype=torch.int16, device=self.device)
+        hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        rc = self.plan.L.spx_edit_replay(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(),
+                                         self.d_nops.data_ptr(), self.d_nout.data_ptr(), tr, d_y.data_ptr(), d_yout.data_ptr(), hs)
+        if rc != 0:
+            raise RuntimeError("spx_edit_replay: " + self.plan.L.spx_last_error().decode())
+        torch.cuda.synchronize(self.device)
+        nout = self.d_nout.cpu().numpy()
+        out = d_yout.cpu().numpy()
+        return [out[tr[i].out_off:tr[i].out_off + max(0, int(nout[i])) * int(ch[i])].copy() for i in range(self.n)]
 
     def tap_arrays(self, i):
         """tension/speed/features rows of stream i (host numpy)."""

@@ -281,6 +281,9 @@ struct SpxCallOpts {
   // spx_batch_run_map: DEVICE, the call's time map (spx_map_rows per job, in job order).  Handled like a rate call: the whole batch on
   // the GENERAL walk kernel (its map instantiation; neither speed-up form writes a map), kernels in sequence on the caller's stream
   int64_t* map = nullptr;
+  // spx_batch_run_edits: the call's edit list.  Handled as a map call is -- the general walk kernel (its recording instantiation),
+  // kernels in sequence on the caller's stream -- and refused together with rate, map or retarget
+  const SpxEditsCall* edits = nullptr;
   // spx_batch_run_twopass's second pass: the speeds come from the device.  Handled like a rate call and a map call -- kernels in
   // sequence on the caller's stream -- but on the walk kernels' any-speed forms (the speed class is "any speed", whatever the
   // placeholder in the host table says); with do_a = false the pass reuses the frame records the first pass left in the workspace

@@ -161,10 +161,10 @@ Layout layout_for(const SpxPlanDev& d, const spx_stream_job* jobs, int n) {
 // Fills tables, judges nothing: the jobs have passed spx_check_jobs at the call's top.
 static void build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n, int nch,
                           std::vector<SpxStreamDev>& v, std::vector<int>& tiles_per_chunk, const SpxRateCall* rc = nullptr,
-                          bool with_map = false) {
+                          bool with_map = false, const int64_t* ops_cap = nullptr) {
   v.resize((size_t)n * nch);
   tiles_per_chunk.assign(nch, 0);
-  int64_t fo = 0, map_row = 0;
+  int64_t fo = 0, map_row = 0;   // (map_row: rows of the time map, or -- ops_cap -- records of the edit list)
   const int TF = d.tile_frames;
   for (int i = 0; i < n; i++) {
     const spx_stream_job& j = jobs[i];
@@ -189,10 +189,10 @@ static void build_streams(const SpxPlanDev& d, const spx_stream_job* jobs, int n
       s.first_tile = tiles_per_chunk[c];
       tiles_per_chunk[c] += (int)((T - Tprev + TF - 1) / TF);
       Tprev = T;
-      if (with_map) s.map_row = (int32_t)map_row;   // (spx_batch_run_map has refused a table of 2^31 rows or more)
+      if (with_map || ops_cap) s.map_row = (int32_t)map_row;   // (spx_batch_run_map has refused a table of 2^31 rows or more, spx_batch_run_edits one of as many records)
     }
     fo += Ttot;
-    map_row += spx_map_rows(d, j.n_in, nonlinear);
+    map_row += ops_cap ? ops_cap[i] : spx_map_rows(d, j.n_in, nonlinear);
   }
 }
 
@@ -501,7 +501,7 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   const SpxForce* force = opt.force;
   // the choke point every call passes: a table that is refused has changed nothing of the plan and enqueued nothing
   // (general: the call runs on the general walk kernel whatever its speeds -- a rate call, a call with a time map)
-  const bool general = opt.rate != nullptr || opt.map != nullptr;
+  const bool general = opt.rate != nullptr || opt.map != nullptr || opt.edits != nullptr;
   if (spx_check_jobs(plan, jobs, n, general, force && force->no_exclusive, opt.retarget != nullptr)) return -1;
   SpxRange range_(do_a && do_w ? "spx_batch_run" : (do_a ? "spx_batch_analyze" : "spx_batch_walk"));
   SpxPlanDev d = plan->dev;  // a copy: the tile size is chosen per call
@@ -563,14 +563,18 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
   // ---- execute ----
   std::vector<SpxStreamDev> sv;
   std::vector<int> tiles;
-  build_streams(d, jobs, n, nch, sv, tiles, opt.rate, opt.map != nullptr);
+  build_streams(d, jobs, n, nch, sv, tiles, opt.rate, opt.map != nullptr, opt.edits ? opt.edits->ops_cap : nullptr);
   if (opt.rate && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_rate: internal: not a plain call in sequence");
   // (a rate call with a map: both conditions hold, the same kernel serves both -- spx_batch_run_rate_map)
   if (opt.map && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force)) return fail(-1, "spx_batch_run_map: internal: not a plain call in sequence");
-  if (retarget && (concurrent || ahead || chunk_ahead || !do_w || force || opt.rate || opt.map || opt.ahead_req || opt.detached))
+  if (opt.edits && (concurrent || ahead || chunk_ahead || !do_a || !do_w || force || opt.rate || opt.map || retarget))
+    return fail(-1, "spx_batch_run_edits: internal: not a plain call in sequence");
+  if (retarget && (concurrent || ahead || chunk_ahead || !do_w || force || opt.rate || opt.map || opt.edits || opt.ahead_req || opt.detached))
     return fail(-1, "spx_batch_run_twopass: internal: not a plain call in sequence");
   if (opt.map && (R.walk.fast_kernel || spx_walk_config(d, {.n_streams = n, .max_channels = maxC}).mode != 0))
     return fail(-1, "spx_batch_run_map: internal: no general walk kernel for this batch");
+  if (opt.edits && (R.walk.fast_kernel || spx_walk_config(d, {.n_streams = n, .max_channels = maxC}).mode != 0))
+    return fail(-1, "spx_batch_run_edits: internal: no general walk kernel for this batch");
   unsigned char* w = static_cast<unsigned char*>(ws);
   SpxStreamDev* dstreams = reinterpret_cast<SpxStreamDev*>(w + L.off_streams);
   SpxStreamState* states = reinterpret_cast<SpxStreamState*>(w + L.off_states);
@@ -721,7 +725,7 @@ int run_impl(const SpxCall& call, const SpxCallOpts& opt) {
         const SpxWalkAsk ask = {.n_streams = n, .max_channels = maxC, .speedup_only = speedup_only, .any_speed = any_speed, .lean = M.launch_lean,
                                 .short_window = short_window_res || (!force && M.walk2 && !M.launch_lean && maxC > 1)};
         spx_launch_walk(d, ask, dj, in, out, opt.rate ? opt.rate->d_tsm_n : n_out, states, scratch, (concurrent || ahead) ? d_ready : nullptr,
-                        (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, stw, opt.map);
+                        (M.exclusive_cu && !(force && force->no_exclusive)) ? R.lds_per_cu / 2 + 1024 : 0, stw, opt.map, opt.edits);
       }
       if (opt.rate && c == nch - 1) {   // the rate stage: TSM buffer -> the caller's out, final counts -> n_out
         SpxTimed tm(timed, 3, stw);

@@ -109,7 +109,8 @@ struct SpxStreamDev {
   int32_t tension_to;    // SPX_F_TENSION_RANGE: compute tension frames [tension_skip, tension_to)
   int32_t handed_in;     // SPX_F_HANDED_IN: ring buffers handed to the TSM stage before this job ...
   int32_t ring_bufs;     // ... and complete ring buffers that exist (n_in is the TSM input's length there, not the ring's)
-  int32_t map_row;       // spx_batch_run_map: index of this stream's row 0 in the call's time map (read by spx_walk_map_kernel only)
+  int32_t map_row;       // spx_batch_run_map: index of this stream's row 0 in the call's time map (read by spx_walk_map_kernel only);
+                         // spx_batch_run_edits: index of this stream's record 0 in the call's edit list (spx_walk_edits_kernel)
 };
 
 // TSM-stage state (libsonic's stream struct) in absolute stream coordinates.
@@ -234,6 +235,7 @@ struct SpxKernelChoice {
 using SpxAnalysisArgs = void(SpxPlanDev, const SpxStreamDev*, int, const int16_t*, SpxFrameRec*, SpxTapsDev, const int*, int*, const float*, int);
 using SpxWalkArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, int, const int*);
 using SpxWalkMapArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, int, const int*, int64_t*);
+using SpxWalkEditsArgs = void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, int, const int*, int4*, int64_t*, int);
 using SpxWalkFastArgs =void(SpxPlanDev, const SpxStreamDev*, const int16_t*, int16_t*, int64_t*, SpxStreamState*, const float*, const int*, int);
 template <typename F> struct SpxLaunch;
 template <typename... P> struct SpxLaunch<void(P...)> {
@@ -264,11 +266,20 @@ struct SpxWalkAsk {
   // two calls' walk workgroups AND an analysis workgroup on a CU -- a mixed call whose walk kernels overlap the previous call's)
   bool short_window = false;
 };
+// What spx_batch_run_edits hands down (SpxCallOpts::edits): the caller's edit list.  ops: DEVICE, 16-byte records, stream i's from
+// the sum of ops_cap[0 .. i) on; ops_cap: HOST; n_ops: DEVICE, the counts; total: the sum of all capacities (below 2^31).
+struct SpxEditsCall {
+  void* ops;
+  const int64_t* ops_cap;
+  int64_t* n_ops;
+  int64_t total;
+};
 // lds_min: the caller wants the workgroups ONE to a CU (it asks for more than half a CU's LDS, spx_engine.hip); 0 otherwise
 // map: DEVICE, the call's time map (spx_batch_run_map: the general kernel's map instantiation, SpxStreamDev::map_row), or null
+// edits: the call's edit list (spx_batch_run_edits: the general kernel's recording instantiation), or null
 void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStreamDev* streams, const int16_t* in, int16_t* out,
                      int64_t* n_out, SpxStreamState* states, const float* scratch, const int* speed_ready, size_t lds_min,
-                     hipStream_t st, int64_t* map = nullptr);
+                     hipStream_t st, int64_t* map = nullptr, const SpxEditsCall* edits = nullptr);
 // mono: every stream of the launch has one channel (the 16 kHz 16-frame instantiation then reads its samples from global memory and
 // asks for no staged span)
 size_t spx_analysis_lds_bytes(const SpxPlanDev& P, bool mono);
@@ -290,6 +301,7 @@ struct SpxWalkConfig {
 SpxWalkConfig spx_walk_config(const SpxPlanDev& P, const SpxWalkAsk& ask);
 SpxKernelChoice spx_walk_select(int nw, int mode);   // spx_walk.hip: the general kernel, waves per stream and mode
 SpxKernelChoice spx_walk_map_select(int nw);         // ... and its instantiation that writes a time map (mode 0)
+SpxKernelChoice spx_walk_edits_select(int nw);       // ... and the one that records an edit list (mode 0)
 // spx_walk_fast.hip
 size_t spx_walk_fast_lds_bytes(const SpxPlanDev& P, int wcap);
 bool spx_walk_fast_supports(const SpxPlanDev& P, int nwm);

@@ -74,6 +74,8 @@ extern "C" void spx_debug_stamps(unsigned long long* out, int reset) {
 struct WalkCtx {
   int* flush_rem;     // SPX_F_NO_TRUNC: where the flush leaves {frames the stage held, frames produced so far} (nullptr: truncate as usual)
   int64_t* map;       // time map (spx_walk_map_kernel): the stream's rows, row k = frames produced when ring buffer k is handed over (nullptr: none)
+  int4* ops;          // edit list (spx_walk_edits_kernel): the stream's records, {out_at, a, b, n} each (record_op)
+  int ops_cap, n_ops; // ... how many fit there, and how many the stream has had so far (counted on past the capacity, stored below it)
   const int16_t* in;  // stream input (interleaved)
   int16_t* out;       // stream output
   pos_t out_cap;
@@ -459,8 +461,20 @@ __device__ __forceinline__ void emit_overlap_add(const WalkCtx& X, pos_t a_down,
   }
 }
 
+// Edit list (spx_walk_edits_kernel; include/speedy_hip.h "EDIT LIST"): one record per emit_copy / emit_overlap_add of n >= 1 frames,
+// written where tsm_process calls them -- a copy is {out_at, a, -1, n}, a cross-fade {out_at, a_down, a_up, n}.  Thread 0 writes one
+// 16-byte store that nobody waits for; past the stream's capacity the count goes on and nothing is stored.
+template <bool EDITS>
+__device__ __forceinline__ void record_op(WalkCtx& X, pos_t out_at, pos_t a, pos_t b, pos_t n) {
+  if constexpr (EDITS) {
+    if (n < 1) return;
+    if (X.n_ops < X.ops_cap && threadIdx.x == 0) X.ops[X.n_ops] = make_int4((int)out_at, (int)a, (int)b, (int)n);
+    X.n_ops++;
+  }
+}
+
 // processStreamInput with `avail` frames handed over so far (absolute count).
-template <int NW, int FAST>
+template <int NW, int FAST, bool EDITS = false>
 __device__ __forceinline__ void tsm_process(const SpxPlanDev& P, WalkCtx& X, WalkState& st, float speed, pos_t avail) {
   const int maxRequired = P.maxRequired;
   if ((double)speed > 1.00001 || (double)speed < 0.99999) {
@@ -471,6 +485,7 @@ __device__ __forceinline__ void tsm_process(const SpxPlanDev& P, WalkCtx& X, Wal
       if (st.remaining > 0) {
         int n = st.remaining;
         if (n > maxRequired) n = maxRequired;
+        record_op<EDITS>(X, st.out_n, st.base + position, -1, n);
         emit_copy<NW, FAST>(X, st, st.base + position, n);
         st.remaining -= n;
         position += n;
@@ -488,6 +503,7 @@ __device__ __forceinline__ void tsm_process(const SpxPlanDev& P, WalkCtx& X, Wal
           if (st.out_n + n > X.out_cap) st.overflow = 1;
           if (n == 0) return;  // the dependency treats this as failure and leaves the input untouched
           STAMP(11);
+          record_op<EDITS>(X, st.out_n, pos, pos + period, n);
           emit_overlap_add<NW, FAST>(X, pos, pos + period, n, st.out_n);
           STAMP(13);
           st.out_n += n;
@@ -500,9 +516,11 @@ __device__ __forceinline__ void tsm_process(const SpxPlanDev& P, WalkCtx& X, Wal
             n = period;
             st.remaining = uni((int)((float)period * (2.0f * speed - 1.0f) / (1.0f - speed)));
           }
+          record_op<EDITS>(X, st.out_n, pos, -1, period);
           emit_copy<NW, FAST>(X, st, pos, period);
           if (st.out_n + n > X.out_cap) st.overflow = 1;
-          if (n == 0) return;
+          if (n == 0) return;   // (a failed step leaves its copy, and its record)
+          record_op<EDITS>(X, st.out_n, pos + period, pos, n);
           emit_overlap_add<NW, FAST>(X, pos + period, pos, n, st.out_n);
           st.out_n += n;
           position += n;
@@ -511,6 +529,7 @@ __device__ __forceinline__ void tsm_process(const SpxPlanDev& P, WalkCtx& X, Wal
     } while (position + maxRequired <= numSamples);
     st.base += position;
   } else {
+    record_op<EDITS>(X, st.out_n, st.base, -1, avail - st.base);
     emit_copy<NW, FAST>(X, st, st.base, avail - st.base);
     st.base = avail;
   }
@@ -668,13 +687,18 @@ static __host__ __device__ inline WalkLds walk_lds_layout(const SpxPlanDev& P, i
 
 // The body of the walk kernels.  MAP (spx_walk_map_kernel, FAST == 0 only): the stream's time-map rows are written as the events
 // go by -- everything that belongs to the map sits behind `if constexpr (MAP)`, so spx_walk_kernel's instantiations compile from
-// the code they always compiled from.
-template <int NW, int FAST, bool MAP>
+// the code they always compiled from.  EDITS (spx_walk_edits_kernel, FAST == 0 only): the stream's edit list, behind `if constexpr
+// (EDITS)` in the same way (record_op).  A stream's records start at ops_base[map_row] -- the job record's row field counts records
+// in such a call -- and its capacity reaches to the next stream's row (ops_total behind the last).  The running count lives in
+// n_ops between the time chunks of a call: reset under SPX_F_INIT, read back otherwise (minus the count once the capacity is passed).
+template <int NW, int FAST, bool MAP, bool EDITS = false>
 __device__ __forceinline__ void
 walk_body(const SpxPlanDev& P, const SpxStreamDev* __restrict__ streams, const int16_t* __restrict__ in_base,
           int16_t* __restrict__ out_base, int64_t* __restrict__ n_out, SpxStreamState* __restrict__ states,
-          const float* scratch_base, int maxC, const int* speed_ready, int64_t* __restrict__ map_base) {
+          const float* scratch_base, int maxC, const int* speed_ready, int64_t* __restrict__ map_base,
+          int4* __restrict__ ops_base = nullptr, int64_t* __restrict__ n_ops = nullptr, int ops_total = 0) {
   static_assert(!MAP || FAST == 0, "the time map is the general kernel's");
+  static_assert(!EDITS || (FAST == 0 && !MAP), "the edit list is the general kernel's, in a call of its own");
   constexpr int NT = 64 * NW;
   // the walk is the latency-critical chain: where the analysis kernel shares a SIMD, these waves issue first
   __builtin_amdgcn_s_setprio(3);
@@ -710,6 +734,16 @@ walk_body(const SpxPlanDev& P, const SpxStreamDev* __restrict__ streams, const i
   X.flush_rem = (S.flags & SPX_F_NO_TRUNC) ? &states[blockIdx.x].flush_remaining : nullptr;
   X.map = nullptr;
   if constexpr (MAP) X.map = map_base ? map_base + S.map_row : nullptr;
+  if constexpr (EDITS) {
+    const int row1 = blockIdx.x + 1 < gridDim.x ? streams[blockIdx.x + 1].map_row : ops_total;
+    X.ops = ops_base + S.map_row;
+    X.ops_cap = uni(row1 - S.map_row);
+    X.n_ops = 0;
+    if (!(S.flags & SPX_F_INIT)) {
+      const int64_t had = n_ops[blockIdx.x];
+      X.n_ops = uni((int)(had < 0 ? -had : had));
+    }
+  }
   X.in = in_base + S.in_off - S.tsm_shift * S.channels;  // indexed by TSM position (= input frame + flush padding so far)
   X.out = out_base + S.out_off;
   X.out_cap = (pos_t)(S.out_cap > 0x7fffffff ? 0x7fffffff : S.out_cap);
@@ -825,7 +859,7 @@ walk_body(const SpxPlanDev& P, const SpxStreamDev* __restrict__ streams, const i
           // input, never waited for; a linear job's one event has no row of its own)
           if (X.map && nl != 0.0f && ev < ev1 && tid == 0) X.map[ev] = (int64_t)st.out_n;
         }
-        tsm_process<NW, FAST>(P, X, st, curSpeed, avail);
+        tsm_process<NW, FAST, EDITS>(P, X, st, curSpeed, avail);
         STAMP(12);
         if (ev >= ev1) {
           if (st.out_n > expected) st.out_n = expected;
@@ -850,6 +884,7 @@ walk_body(const SpxPlanDev& P, const SpxStreamDev* __restrict__ streams, const i
       // the last row: the job's final count, behind flush and truncation (a linear job's only row)
       if (X.map && do_flush) X.map[nl != 0.0f ? S.n_in / B : 0] = st.overflow == 2 ? INT64_MIN : (st.overflow ? -(int64_t)st.out_n : (int64_t)st.out_n);
     }
+    if constexpr (EDITS) n_ops[blockIdx.x] = X.n_ops > X.ops_cap ? -(int64_t)X.n_ops : (int64_t)X.n_ops;
   }
 }
 
@@ -867,6 +902,16 @@ spx_walk_map_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, cons
                     int16_t* __restrict__ out_base, int64_t* __restrict__ n_out, SpxStreamState* __restrict__ states,
                     const float* scratch_base, int maxC, const int* speed_ready, int64_t* __restrict__ map_base) {
   walk_body<NW, 0, true>(P, streams, in_base, out_base, n_out, states, scratch_base, maxC, speed_ready, map_base);
+}
+// The general kernel with an edit list (spx_batch_run_edits): stream i's records at ops_base[streams[i].map_row ...], counts in n_ops.
+template <int NW>
+__global__ void __launch_bounds__(64 * NW)
+spx_walk_edits_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, const int16_t* __restrict__ in_base,
+                      int16_t* __restrict__ out_base, int64_t* __restrict__ n_out, SpxStreamState* __restrict__ states,
+                      const float* scratch_base, int maxC, const int* speed_ready, int4* __restrict__ ops_base,
+                      int64_t* __restrict__ n_ops, int ops_total) {
+  walk_body<NW, 0, false, true>(P, streams, in_base, out_base, n_out, states, scratch_base, maxC, speed_ready, nullptr, ops_base, n_ops,
+                                ops_total);
 }
 
 // Which kernel variant a batch gets: 0 general, 1 speed-up mono, 2 speed-up multi-channel.  FAST: all streams speeding
@@ -968,6 +1013,12 @@ SpxKernelChoice spx_walk_map_select(int nw) {
   if (nw == 8) return SpxKernelChoice{"spx_walk_map_kernel", reinterpret_cast<const void*>(spx_walk_map_kernel<8>), 64 * 8, 1, {8}};
   return SpxKernelChoice{"spx_walk_map_kernel", reinterpret_cast<const void*>(spx_walk_map_kernel<4>), 64 * 4, 1, {4}};
 }
+// ... and of the general kernel that records an edit list (mode 0 only, as the map's).
+SpxKernelChoice spx_walk_edits_select(int nw) {
+  static_assert(std::is_same<decltype(spx_walk_edits_kernel<8>), SpxWalkEditsArgs>::value, "SpxWalkEditsArgs is the kernel's argument list");
+  if (nw == 8) return SpxKernelChoice{"spx_walk_edits_kernel", reinterpret_cast<const void*>(spx_walk_edits_kernel<8>), 64 * 8, 1, {8}};
+  return SpxKernelChoice{"spx_walk_edits_kernel", reinterpret_cast<const void*>(spx_walk_edits_kernel<4>), 64 * 4, 1, {4}};
+}
 int spx_walk_vgprs(const SpxPlanDev& P, const SpxWalkAsk& ask, int* scratch_bytes) {
   return spx_kernel_vgprs(spx_walk_config(P, ask).kernel.fn, scratch_bytes);
 }
@@ -980,7 +1031,7 @@ extern "C" int spx_debug_last_walk_form(void) { return g_last_walk_form.load(std
 
 void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStreamDev* streams, const int16_t* in, int16_t* out,
                      int64_t* n_out, SpxStreamState* states, const float* scratch, const int* speed_ready, size_t lds_min,
-                     hipStream_t st, int64_t* map) {
+                     hipStream_t st, int64_t* map, const SpxEditsCall* edits) {
   const int n_streams = ask.n_streams;
   if (n_streams <= 0) return;
   const int maxC = ask.max_channels < 1 ? 1 : ask.max_channels;
@@ -991,6 +1042,15 @@ void spx_launch_walk(const SpxPlanDev& P, const SpxWalkAsk& ask, const SpxStream
     if (cfg.fast_kernel || cfg.mode != 0) return;
     g_last_walk_form.store(0, std::memory_order_relaxed);
     SpxLaunch<SpxWalkMapArgs>::go(spx_walk_map_select(cfg.nw), n_streams, cfg.lds, st, P, streams, in, out, n_out, states, scratch, maxC, speed_ready, map);
+    return;
+  }
+  if (edits) {
+    // an edit list: the general kernel's recording instantiation, same waves and LDS (run_impl has refused, before it enqueued
+    // anything, a call whose shape asks for a speed-up form)
+    if (cfg.fast_kernel || cfg.mode != 0) return;
+    g_last_walk_form.store(0, std::memory_order_relaxed);
+    SpxLaunch<SpxWalkEditsArgs>::go(spx_walk_edits_select(cfg.nw), n_streams, cfg.lds, st, P, streams, in, out, n_out, states, scratch, maxC, speed_ready,
+                                    reinterpret_cast<int4*>(edits->ops), edits->n_ops, (int)edits->total);
     return;
   }
   g_last_walk_form.store(cfg.fast_kernel ? 16 * cfg.nwm + cfg.nwc : 0, std::memory_order_relaxed);
