@@ -251,6 +251,57 @@ int spx_edit_replay(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, 
                     const int64_t* n_ops, const int64_t* n_out, const spx_edit_track* tracks, const int16_t* y_in, int16_t* y_out,
                     void* hip_stream);
 
+/* ---- BATCH DTW: align pairs of feature sequences on the device -- cost, warp path and slopes per pair ----
+ * The reference's perceptual check (TestSpeechSample, sonic_test.cc:639-724) aligns the spectrogram of the output to that of the
+ * input by dynamic time warping (dynamic_time_warping.{h,cc}) and asks whether the warp path has the slope the speed promised.
+ * spx_batch_dtw does that for a batch of pairs in device memory -- the `spectrogram` tap of spx_batch_run / spx_batch_analyze can be
+ * handed over where it lies -- and leaves cost, path and slope figures in device memory.  tests/dtw_ref.py states the definition
+ * in Python float32 scalars; the kernels are held to it bit for bit.
+ *
+ * For sequences a (n_a rows) and b (n_b rows) of dim floats:
+ *   local cost   d(i, j): s = 0; for k = 0 .. dim - 1 IN THIS ORDER: t = a[i][k] - b[j][k], s = s + t * t; d = sqrtf(s).  Every
+ *                operation rounded to float, no fused multiply-add, the square root correctly rounded (EuclideanDistance,
+ *                sonic_test.cc:200-209).
+ *   recurrence   (dynamic_time_warping.cc:76-100)  C(0,0) = d(0,0), direction 0; first row C(0,j) = d(0,j) + C(0,j-1), direction
+ *                +1; first column C(i,0) = d(i,0) + C(i-1,0), direction -1; elsewhere, with up = C(i-1,j), left = C(i,j-1),
+ *                diag = C(i-1,j-1): C(i,j) = d(i,j) + min(min(up, left), diag), direction -1 if up < diag && up < left, +1 if
+ *                left < up && left < diag, else 0 -- strict comparisons, ties go along the diagonal.  cost = C(n_a-1, n_b-1).
+ *   path         (:102-132)  from (n_a-1, n_b-1): record (i, j); direction -1: i--, 0: i--, j--, +1: j--; until an index is below
+ *                0.  Reversed: n_path <= n_a + n_b - 1 pairs, the first (0, 0).
+ *   slope        (LinearSlope, sonic_test.cc:86-99)  x = the path's a indices, y = its b indices; four float sums added in path
+ *                order, x*y and x*x formed as exact integers and then converted; slope = (n*sumXY - sumX*sumY) / (n*sumX2 -
+ *                sumX*sumX) in float, n = (float)n_path.
+ *   local slopes (LinearSlopeEverywhere, VectorMean, VectorStandardDeviation, :101-133)  window p = the same slope over path
+ *                entries p - h .. p + h - 1, p = h .. n_path - h - 1: n_local = max(0, n_path - 2 h) of them.  local_mean: the
+ *                slopes added in order in a double, rounded to float, divided by (float)n_local.  local_std: diff = slope - mean
+ *                and diff * diff in float, added in order in a double, rounded to float, divided by (float)n_local, sqrtf.
+ * A zero denominator -- n_path = 1, a window in which a does not advance, n_local = 0 -- gives what IEEE arithmetic gives: NaN or
+ * an infinity.  DOMAIN: finite inputs whose accumulated costs stay finite; outside it the results are unspecified.
+ *
+ *   jobs      HOST   one per pair: a_off / b_off = the first value of the pair's rows, in floats from a / b; path_off = its first
+ *                    path entry, in entries (int32 pairs: a index, b index) from `path`; n_a, n_b >= 1 rows, n_a * n_b <= 2^30
+ *   dim       values per row that take part, 1 .. 65536;  ld_a, ld_b >= dim: floats from one row to the next.  Values at or behind
+ *             column dim of a row are never read: with ld = N (spx_plan_fft_size) and dim = N / 4 the spectrogram tap is aligned
+ *             in place on its low bins, as the reference's ComputeSpectrogram keeps them.
+ *   a, b      DEVICE float rows;  results  DEVICE [n_pairs];  path  DEVICE: n_a + n_b - 1 entries per pair from path_off -- the
+ *             regions are the caller's, not checked for overlap; entries at or behind n_path are not written
+ *   workspace DEVICE, spx_dtw_workspace_bytes (0 with spx_last_error for a table the call refuses): two bits per cell of direction,
+ *             rounded up to 64 columns, and 16 bytes per row and column -- the cost matrix itself is never stored
+ *   plan      the device, and the staging of the job table: what spx_edit_replay and spx_map_lookup use it for.  The sample rate
+ *             plays no part.
+ * Asynchronous on hip_stream; nothing comes back to the host.  Refused with -1 and spx_last_error, nothing enqueued, the outputs
+ * untouched: a NULL pointer; n_pairs < 1; dim < 1 or above 65536; a row stride below dim; half_width < 1; n_a or n_b below 1;
+ * n_a * n_b > 2^30; a negative offset; a workspace below spx_dtw_workspace_bytes.
+ * COST: one workgroup per pair -- a pair's recurrence is one chain -- in two launches; profiles/dtw.txt.
+ * OUT OF SCOPE: a distance other than the Euclidean one; banded or windowed warping; a pipeline-object form; DTW inside the _run
+ * calls. */
+typedef struct { int64_t a_off, b_off; int64_t path_off; int32_t n_a, n_b; } spx_dtw_job;                             /* HOST, 32 bytes */
+typedef struct { float cost, slope, local_mean, local_std; int32_t n_path, n_local; } spx_dtw_result;                 /* DEVICE, 24 bytes */
+size_t spx_dtw_workspace_bytes(const spx_dtw_job* jobs, int n_pairs, int dim);
+int spx_batch_dtw(spx_plan_t plan, const spx_dtw_job* jobs, int n_pairs, int dim, int ld_a, int ld_b, int half_width,
+                  const float* a, const float* b, spx_dtw_result* results, int32_t* path,
+                  void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- TWO PASSES IN ONE CALL: every stream to a target length, or the linear control at the nonlinear duration ----
  * The reference's CLI has two two-pass drivers (speedy_wave.cc:424-462): --length runs a nonlinear pass at the requested speed,
  * measures what came out and runs the final pass at want * (want / achieved), so that the output lands on the requested duration;
@@ -619,6 +670,8 @@ int spx_debug_last_call_chunks(void);
 int spx_debug_last_lookup_grid(int* launches);
 /* ... and the output blocks per stream of the last spx_edit_replay (4 096 int16 values each), with its launches. */
 int spx_debug_last_replay_grid(int* launches);
+/* ... and the workgroups of the last spx_batch_dtw: one per pair, in each of its two launches (*launches = 2). */
+int spx_debug_last_dtw_grid(int* launches);
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls);
 /* "analysis;tension;walk": the kernels (template arguments included, as a profiler prints them) that serve a batch of
  * n_streams streams with at most max_channels channels; speedup_only = every job has speed > 1. */
@@ -690,6 +743,10 @@ double spx_timing_last_tension_ms(void);
 double spx_timing_last_rate_ms(void);
 /* ... and of the kernel that converts a time map's rows to final frames (spx_batch_run_rate_map / _float_map calls with a rate other than 1). */
 double spx_timing_last_map_rows_ms(void);
+/* ... and of the two kernels of the spx_batch_dtw calls made while spx_set_timing was on, and the share of the second (the
+ * back-trace and the slopes). */
+double spx_timing_last_dtw_ms(void);
+double spx_timing_last_dtw_tail_ms(void);
 
 /* Diagnostics: the number of pitch searches (libsonic's findPitchPeriod calls) each stream's walk has run since the stream started (a batch job starts it) -- the length of the stream's chain of dependent steps, which is what bounds a call with one stream per CU.
  *   workspace  DEVICE  the workspace that call ran with;  steps  HOST  int32[n_streams].  Waits for hip_stream first. */

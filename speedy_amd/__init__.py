@@ -7,3 +7,11 @@ ctypes over the C-ABI, torch only for device memory / streams / torch.distribute
 There is no CPU fallback: without the library or a GPU, calls raise.
 """
 from ._lib import lib, build, LIB_PATH  # noqa: F401
+
+
+def __getattr__(name):
+    # speedy_amd.DtwBatch (speedy_amd/dtw.py), resolved on first use: importing the package alone does not import torch
+    if name == "DtwBatch":
+        from .dtw import DtwBatch
+        return DtwBatch
+    raise AttributeError(name)

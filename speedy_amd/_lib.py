@@ -26,7 +26,11 @@ class EditTrack(C.Structure):  # spx_edit_track
     _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("channels", C.c_int32), ("reserved", C.c_int32)]
 
 
-TENSION_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float)
+class DtwJob(C.Structure):  # spx_dtw_job
+    _fields_ = [("a_off", C.c_int64), ("b_off", C.c_int64), ("path_off", C.c_int64), ("n_a", C.c_int32), ("n_b", C.c_int32)]
+
+
+TENSION_FN =C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_float)
 FEATURES_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, c_float_p)
 
 # name -> (restype, argtypes); every symbol declared in include/speedy_hip.h and include/sonic2.h
@@ -64,7 +68,13 @@ SYMBOLS = {
                                       c_int64_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
     "spx_edit_replay": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(EditTrack), C.c_void_p, C.c_void_p, C.c_void_p]),
-    "spx_batch_workspace_bytes_twopass": (C.c_size_t, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int]),
+    "spx_dtw_workspace_bytes": (C.c_size_t, [C.POINTER(DtwJob), C.c_int, C.c_int]),
+    "spx_batch_dtw": (C.c_int, [C.c_void_p, C.POINTER(DtwJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "spx_debug_last_dtw_grid": (C.c_int, [C.POINTER(C.c_int)]),
+    "spx_timing_last_dtw_ms": (C.c_double, []),
+    "spx_timing_last_dtw_tail_ms": (C.c_double, []),
+    "spx_batch_workspace_bytes_twopass":(C.c_size_t, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int]),
     "spx_plan_out_capacity_twopass": (C.c_int64, [C.c_void_p, C.c_int64, C.c_double, C.c_float]),
     "spx_batch_run_twopass": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),

@@ -82,18 +82,21 @@ void spx_set_tension_form(int form) { g_tension_form = form != 0; }
 int spx_debug_last_tension_form(void) { return g_last_tension_form.load(std::memory_order_relaxed); }
 int spx_debug_last_call_chunks(void) { return g_last_call_chunks.load(std::memory_order_relaxed); }
 void spx_set_pipeline_chunks(int chunks) { g_chunks_set = true; g_chunks = chunks < 1 ? 1 : (chunks > SPX_MAX_CHUNKS ? SPX_MAX_CHUNKS : chunks); }
-static double g_last_tension_ms = 0.0, g_last_rate_ms = 0.0, g_last_map_rows_ms = 0.0;
+static double g_last_tension_ms = 0.0, g_last_rate_ms = 0.0, g_last_map_rows_ms = 0.0, g_last_dtw_ms = 0.0, g_last_dtw_tail_ms = 0.0;
 double spx_timing_last_tension_ms(void) { return g_last_tension_ms; }
 double spx_timing_last_rate_ms(void) { return g_last_rate_ms; }
 double spx_timing_last_map_rows_ms(void) { return g_last_map_rows_ms; }
+double spx_timing_last_dtw_ms(void) { return g_last_dtw_ms; }
+double spx_timing_last_dtw_tail_ms(void) { return g_last_dtw_tail_ms; }
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls) {
   std::lock_guard<std::mutex> g(g_tmu);
-  double a = 0, w = 0, t = 0, r = 0, m = 0;
+  double a = 0, w = 0, t = 0, r = 0, m = 0, df = 0, dt = 0;
   for (auto& ev : g_ev_pending) {
     HIPCHK(hipEventSynchronize(ev.b));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (ev.kind == 0) a += ms; else if (ev.kind == 1) w += ms; else if (ev.kind == 3) r += ms; else if (ev.kind == 4) m += ms; else t += ms;
+    if (ev.kind == 0) a += ms; else if (ev.kind == 1) w += ms; else if (ev.kind == 3) r += ms; else if (ev.kind == 4) m += ms;
+    else if (ev.kind == 5) df += ms; else if (ev.kind == 6) dt += ms; else t += ms;
     g_ev_free.push_back(ev.a);
     g_ev_free.push_back(ev.b);
   }
@@ -101,6 +104,8 @@ int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls
   g_last_tension_ms = t;
   g_last_rate_ms = r;
   g_last_map_rows_ms = m;
+  g_last_dtw_ms = df + dt;
+  g_last_dtw_tail_ms = dt;
   if (sum_ms_analyze) *sum_ms_analyze = a;
   if (sum_ms_walk) *sum_ms_walk = w;
   if (n_calls) *n_calls = g_calls_pending;

@@ -5,6 +5,7 @@
 //   spx_mixed.hip   one call over several plans (BASELINE configs[4])
 //   spx_map.hip     the call with a time map, and the lookup
 //   spx_twopass.hip the two-pass call (a probe pass, then the final pass at a speed worked out on the device), its retarget kernel
+//   spx_dtw.hip     batch dynamic time warping (spx_batch_dtw): its two kernels and the call
 //   spx_convert.hip the call on float samples: two conversions around the int16 call
 //   spx_pipeline.hip the pipeline object: it includes this header for the entries it calls (spx_internal_run*, spx_conv_*)
 //   spx_diag.hip    kernel names, resource queries, timing collection, output packing, small copies
@@ -151,7 +152,7 @@ struct spx_plan {
 };
 
 // ---- process-wide state (spx_engine.hip) ----
-struct EvPair { hipEvent_t a, b; int kind; };  // kind 0 = analysis launch, 1 = walk launch, 2 = tension launch, 3 = rate launch (spx_batch_run_rate), 4 = the map's rows conversion (spx_batch_run_rate_map)
+struct EvPair { hipEvent_t a, b; int kind; };  // kind 0 = analysis launch, 1 = walk launch, 2 = tension launch, 3 = rate launch (spx_batch_run_rate), 4 = the map's rows conversion (spx_batch_run_rate_map), 5 / 6 = the forward / tail kernel of spx_batch_dtw
 extern std::atomic<bool> g_timing;
 extern std::atomic<int> g_last_concurrent;   // spx_debug_last_call_concurrent (2 = pipelined with the previous call)
 extern std::atomic<int> g_concurrent;        // spx_set_concurrent
