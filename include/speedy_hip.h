@@ -128,8 +128,10 @@ int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, f
  *   nonlinear == 0   one row, M[0] = n_out.
  * spx_plan_map_rows returns that row count (-1 for a null plan or a negative n_in).  M[0] = 0 where R >= 1, and the rows never
  * decrease; consecutive rows are often equal, because the time-scale stage works in whole pitch periods.  It also holds back up to
- * about spx_plan_max_required input frames before it emits anything for them: the map is LATE by at most that -- a few tens of
- * milliseconds -- and never early.  (The integral of 1 / speed over the speed tap is no substitute: it drifts from these rows.)
+ * about spx_plan_max_required input frames before it emits anything for them: the map is LATE by at most that much INPUT -- a few
+ * tens of milliseconds; measured against spx_edit_lookup, 480 to 490 of 492 frames at 16 kHz -- and never early.  In OUTPUT frames
+ * the lag is that input at the speed of the moment: up to 221 frames at 3.5x, 428 at 1.2x and 1 579 at 0.5x on the directed 16 kHz
+ * jobs (profiles/edit_lookup.txt).  (The integral of 1 / speed over the speed tap is no substitute: it drifts from these rows.)
  *   map  DEVICE int64; stream i's rows start at the sum of spx_plan_map_rows of the streams in front of it, in job order.
  * out, n_out and the taps are byte for byte spx_batch_run's for the same table; the workspace is spx_batch_workspace_bytes.  The
  * call refuses what spx_batch_run refuses, with the same messages, and a NULL map -- -1, spx_last_error, nothing enqueued.  The rows
@@ -219,8 +221,7 @@ int spx_batch_run_float_map(spx_plan_t plan, const spx_stream_job* jobs, const f
  * misaligned ops, a NULL ops_cap or n_ops; a negative capacity; more than 2^31 - 1 records of capacity in one call.
  * COST: as spx_batch_run_map -- the whole batch on the GENERAL walk kernel, kernels in sequence on hip_stream -- plus one 16-byte
  * store per record.  The plain call only.  OUT OF SCOPE: an edit list on the _rate, _float, _map, _twopass, _ahead, _overlapped and
- * _mixed* calls, on the pipeline object and on the streaming API; float tracks; a sample-exact position lookup over the records
- * (spx_map_lookup answers to 10 ms; the list makes the exact answer possible -- the follow-up).
+ * _mixed* calls, on the pipeline object and on the streaming API; float tracks.
  *
  * spx_plan_edit_ops returns a capacity that holds every record of a job NONE OF WHOSE STEPS FAILS (-1 for values spx_batch_run
  * refuses).  A step fails when its cross-fade would have no frame: with minPeriod = sample rate / 400, a linear job with
@@ -240,7 +241,49 @@ int spx_batch_run_float_map(spx_plan_t plan, const spx_stream_job* jobs, const f
  *   y_in     DEVICE read only below L frames per stream: no padding behind the last track is needed (unlike spx_batch_run's `in`)
  *   y_out    DEVICE a stream with n_out[i] <= 0 or n_ops[i] < 0 gets nothing written; no other gets more than n_out[i] frames
  * Refused with -1 and spx_last_error before anything is enqueued: a NULL pointer; a track with channels < 1 (or above 65535) or a
- * negative offset; a misaligned ops; a table spx_batch_run refuses. */
+ * negative offset; a misaligned ops; a table spx_batch_run refuses.
+ *
+ * POSITION LOOKUP, TO THE SAMPLE: spx_edit_index and spx_edit_lookup answer "where did this input frame go" and "which input frame
+ * plays here" from the records themselves -- exact, and not late, where spx_map_lookup answers to 10 ms and up to about
+ * spx_plan_max_required frames late.  For word or phone labels, caption cues, an editor's cut points, a click in the sped-up audio
+ * that must land on the source.  tests/edit_lookup_ref.py states the definition in Python integers.
+ *   The SOURCE of output frame out_at + t of a record, with h = (n + 1) / 2 (the number of t with 2 t < n):
+ *     copy         a + t
+ *     cross-fade   a + t for t < h (the ramp going down still has the larger weight), b + t from there on (a tie in weight goes
+ *                  to the ramp coming up)
+ *   inverse  (output frame u -> input frame)  u below 0 counts as 0; u >= n_out answers L with record -1; otherwise k = the record
+ *            that covers u, the largest k with out_at(k) <= u, and the answer is min(source, L) with record k -- a frame that plays
+ *            the flush's padding answers L.
+ *   forward  (input frame p -> output frame)  p clamped to [0, L]; the answer is the smallest output frame o < n_out whose source
+ *            is >= p -- the first moment at which p itself is heard, or the first surviving audio behind it -- with its record; n_out
+ *            with record -1 if there is none.
+ * The source is not monotone over the output (a slow-down plays input twice), so forward searches the INDEX: with R_k = the largest
+ * source inside record k (a + n - 1 for a copy; a + h - 1, or max(a + h - 1, b + n - 1) where n > h, for a cross-fade),
+ * G_k = max(R_0 .. R_k).  The first record with G_k >= p holds the answer, at t = max(0, p - a) for a copy, and for a cross-fade
+ * t1 = max(0, p - a) if t1 < h, else max(h, p - b); the answer is min(out_at + t, n_out) -- records behind the flush's cut are in
+ * the list, the min handles them -- and its record is -1 when the answer is n_out.
+ * forward is non-decreasing, forward(inverse(o)) <= o, and inverse(forward(p)) >= p where forward(p) < n_out.
+ *
+ * spx_edit_index writes G, asynchronously on hip_stream; n_ops is read on the device.
+ *   jobs, ops, ops_cap, n_ops   as spx_edit_replay takes them
+ *   index    DEVICE int32, laid out as ops: stream i's values start at the sum of ops_cap of the streams in front of it, one per
+ *            record; exactly min(n_ops[i], ops_cap[i]) are written, none for a stream with a negative n_ops
+ * spx_edit_lookup converts positions, asynchronously on hip_stream.
+ *   n_out    DEVICE as spx_batch_run_edits left it
+ *   index    DEVICE what spx_edit_index wrote for these records; may be NULL where inverse != 0
+ *   q_off, q, r   DEVICE int64, exactly as spx_map_lookup takes them
+ *   rec      DEVICE int32, same indices as r, or NULL: the index of the answer's record in the stream's list (-1: none), so that a
+ *            caller can read both ramps and the weight of a cross-fade from ops itself
+ *   inverse  0: input frame -> output frame; otherwise output frame -> input frame
+ * A stream whose n_ops[i] or n_out[i] is negative gets -1 for every answer and every record, and disturbs no other stream.
+ * Refused with -1 and spx_last_error before anything is enqueued: a NULL pointer other than rec and (inverse != 0) index; a forward
+ * call without an index; a misaligned ops; a negative capacity; more than 2^31 - 1 records of capacity in one call; a table
+ * spx_batch_run refuses.  Whatever the records hold, the kernels read nothing outside the stream's region of ops and index (no
+ * track, no audio) and write nothing outside r, rec and that region of index; on records that are not contiguous from 0 or whose
+ * positions do not fit int32 the answers are unspecified.
+ * COST: the index one workgroup per stream in one pass; a lookup one binary search per query (profiles/edit_lookup.txt).
+ * OUT OF SCOPE: lookups behind a rate stage; lookups on the _float, _twopass, _ahead and _mixed* calls, on the pipeline object and on
+ * the streaming API (none of them records a list); fractional answers inside a cross-fade. */
 typedef struct { int32_t out_at, a, b, n; } spx_edit_op;
 typedef struct { int64_t in_off, out_off; int32_t channels, reserved; } spx_edit_track;
 int64_t spx_plan_edit_ops(spx_plan_t plan, int64_t n_in, float speed, float nonlinear);
@@ -250,6 +293,11 @@ int spx_batch_run_edits(spx_plan_t plan, const spx_stream_job* jobs, int n_strea
 int spx_edit_replay(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const spx_edit_op* ops, const int64_t* ops_cap,
                     const int64_t* n_ops, const int64_t* n_out, const spx_edit_track* tracks, const int16_t* y_in, int16_t* y_out,
                     void* hip_stream);
+int spx_edit_index(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const spx_edit_op* ops, const int64_t* ops_cap,
+                   const int64_t* n_ops, int32_t* index, void* hip_stream);
+int spx_edit_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const spx_edit_op* ops, const int64_t* ops_cap,
+                    const int64_t* n_ops, const int64_t* n_out, const int32_t* index, const int64_t* q_off, const int64_t* q,
+                    int64_t* r, int32_t* rec, int inverse, void* hip_stream);
 
 /* ---- BATCH DTW: align pairs of feature sequences on the device -- cost, warp path and slopes per pair ----
  * The reference's perceptual check (TestSpeechSample, sonic_test.cc:639-724) aligns the spectrogram of the output to that of the
@@ -670,6 +718,8 @@ int spx_debug_last_call_chunks(void);
 int spx_debug_last_lookup_grid(int* launches);
 /* ... and the output blocks per stream of the last spx_edit_replay (4 096 int16 values each), with its launches. */
 int spx_debug_last_replay_grid(int* launches);
+/* ... and the query blocks per stream of the last spx_edit_lookup (4 .. 1 024, chosen as spx_map_lookup chooses them), with its launches. */
+int spx_debug_last_edit_lookup_grid(int* launches);
 /* ... and the workgroups of the last spx_batch_dtw: one per pair, in each of its two launches (*launches = 2). */
 int spx_debug_last_dtw_grid(int* launches);
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls);

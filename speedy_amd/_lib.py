@@ -68,6 +68,9 @@ SYMBOLS = {
                                       c_int64_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Taps), C.c_void_p]),
     "spx_edit_replay": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(EditTrack), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spx_edit_index": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spx_edit_lookup": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "spx_dtw_workspace_bytes": (C.c_size_t, [C.POINTER(DtwJob), C.c_int, C.c_int]),
     "spx_batch_dtw": (C.c_int, [C.c_void_p, C.POINTER(DtwJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -112,6 +115,7 @@ SYMBOLS = {
     "spx_debug_last_call_chunks": (C.c_int, []),
     "spx_debug_last_lookup_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_debug_last_replay_grid": (C.c_int, [C.POINTER(C.c_int)]),
+    "spx_debug_last_edit_lookup_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_timing_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "spx_timing_last_tension_ms": (C.c_double, []),
     "spx_timing_last_rate_ms": (C.c_double, []),

@@ -55,7 +55,11 @@ class Batch:
     edits: run() is spx_batch_run_edits -- the same outputs, counts and taps, and the jobs' edit lists beside them: edits(i) returns
     stream i's records (out_at, a, b, n), replay(tracks, channels) applies the lists to companion tracks of the same lengths on the
     GPU (spx_edit_replay).  The capacities are spx_plan_edit_ops' (ops_caps: one value or one per stream instead); not together
-    with rate or time_map.  The plain call only."""
+    with rate or time_map.  The plain call only.  locate(i, positions) and locate_all(positions) convert positions through the lists
+    to the sample (spx_edit_lookup), where lookup answers to 10 ms."""
+
+    d_index = None          # the running maximum spx_edit_index writes, beside d_ops: made at the first forward locate
+    _index_built = False    # ... and valid until the next run()
 
     def __init__(self, plan, lengths, channels, speed, nonlinear=1.0, feedback=0.0, device="cuda", taps=False,
                  spectrogram_taps=False, rate=None, time_map=False, edits=False, ops_caps=None):
@@ -203,6 +207,7 @@ class Batch:
                                                  self.d_nout.data_ptr(), self.d_ops.data_ptr(), self._ops_cap_ptr(),
                                                  self.d_nops.data_ptr(), self.d_ws.data_ptr(), self.d_ws.numel(),
                                                  C.byref(self.taps) if self.taps is not None else None, hs)
+            self._index_built = False
             if rc != 0:
                 raise RuntimeError("spx_batch_run_edits: " + self.plan.L.spx_last_error().decode())
             return
@@ -363,6 +368,55 @@ class Batch:
         nout = self.d_nout.cpu().numpy()
         out = d_yout.cpu().numpy()
         return [out[tr[i].out_off:tr[i].out_off + max(0, int(nout[i])) * int(ch[i])].copy() for i in range(self.n)]
+
+    def locate_all(self, positions, inverse=False, records=False, stream=None):
+        """spx_edit_lookup over the whole batch, to the sample: positions[i] = stream i's queries (any int sequence, may be empty).
+        Input frames to the output frame each is first heard at; inverse=True: output frames to the input frame each plays
+        (include/speedy_hip.h "POSITION LOOKUP").  Returns a list of int64 numpy arrays; records=True: (that list, a list of int32
+        arrays with the index of each answer's record in edits(i), -1 where there is none).  The index a forward lookup searches
+        (spx_edit_index) is built at the first one after a run()."""
+        if not self.with_edits:
+            raise ValueError("the batch was made without edits=True")
+        assert len(positions) == self.n
+        qs = [np.ascontiguousarray(p, np.int64).ravel() for p in positions]
+        offs = np.zeros(self.n + 1, np.int64)
+        offs[1:] = np.cumsum([q.size for q in qs])
+        total = int(offs[-1])
+        d_off = torch.from_numpy(offs).to(self.device)
+        d_q = torch.from_numpy(np.concatenate(qs) if total else np.zeros(1, np.int64)).to(self.device)
+        d_r = torch.zeros_like(d_q)
+        d_rec = torch.zeros(d_q.numel(), dtype=torch.int32, device=self.device) if records else None
+        L = self.plan.L
+        hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if not inverse and not self._index_built:
+            if self.d_index is None:
+                self.d_index = torch.zeros(max(1, self.op_offs[-1]), dtype=torch.int32, device=self.device)
+            rc = L.spx_edit_index(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
+                                  self.d_index.data_ptr(), hs)
+            if rc != 0:
+                raise RuntimeError("spx_edit_index: " + L.spx_last_error().decode())
+            self._index_built = True
+        rc = L.spx_edit_lookup(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
+                               self.d_nout.data_ptr(), None if inverse else self.d_index.data_ptr(), d_off.data_ptr(), d_q.data_ptr(),
+                               d_r.data_ptr(), d_rec.data_ptr() if records else None, 1 if inverse else 0, hs)
+        if rc != 0:
+            raise RuntimeError("spx_edit_lookup: " + L.spx_last_error().decode())
+        torch.cuda.synchronize(self.device)
+        res = d_r.cpu().numpy()
+        ans = [res[int(offs[i]):int(offs[i + 1])].copy() for i in range(self.n)]
+        if not records:
+            return ans
+        rec = d_rec.cpu().numpy()
+        return ans, [rec[int(offs[i]):int(offs[i + 1])].copy() for i in range(self.n)]
+
+    def locate(self, i, positions, inverse=False, records=False):
+        """Stream i's positions through its edit list: input frames to output frames (inverse=True: the other way); records=True:
+        (answers, record indices)."""
+        if not self.with_edits:
+            raise ValueError("the batch was made without edits=True")
+        empty = np.zeros(0, np.int64)
+        got = self.locate_all([positions if k == i else empty for k in range(self.n)], inverse, records)
+        return (got[0][i], got[1][i]) if records else got[i]
 
     def tap_arrays(self, i):
         """tension/speed/features rows of stream i (host numpy)."""
