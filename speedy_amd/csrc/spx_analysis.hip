@@ -165,6 +165,28 @@ __device__ __forceinline__ float spx_untangle_mag(double ar, double ai, double b
   return spx_sqrt64_to_f32(0.25 * __builtin_fma(xr2, xr2, xi2 * xi2));
 #endif
 }
+// Bins k and W - k in one go: (ar, ai) = Z[k], (cr, ci) = Z[W-k], w the factor of bin k.  mk is spx_untangle_mag(ar, ai, cr, -ci, w).
+// Bin W - k is made of the same two points with their roles exchanged and of the factor (-w.x, +w.y) (the table says so bit for bit:
+// tests/test_untangle_table.py, and spx_plan_create checks it), so each of its four sums and differences is bin k's or its exact
+// negative:  ci + ai and cr + ar are bin k's di and ar + b_r (an addition commutes),  cr - ar = -dr,  ci - ai = -(ai + b_i)  (a
+// difference taken the other way round is the exact negative).  Every product below then has bin k's operands or their exact
+// negatives, and rounding commutes with negation: mw is spx_untangle_mag(cr, ci, ar, -ai, (-w.x, w.y)) bit for bit, four
+// additions and two LDS reads cheaper.
+__device__ __forceinline__ void spx_untangle_mag_pair(double ar, double ai, double cr, double ci, double2 w, float& mk, float& mw) {
+#ifdef SPX_DFT_V1
+  mk = spx_untangle_mag(ar, ai, cr, -ci, w);
+  mw = spx_untangle_mag(cr, ci, ar, -ai, make_double2(-w.x, w.y));
+#else
+  const double b_r = cr, b_i = -ci;
+  const double dr = ar - b_r, di = ai - b_i, sr = ar + b_r, si = ai + b_i;
+  const double xr2 = __builtin_fma(w.x, di, __builtin_fma(w.y, dr, sr));
+  const double xi2 = __builtin_fma(w.y, di, __builtin_fma(-w.x, dr, si));
+  mk = spx_sqrt64_to_f32(0.25 * __builtin_fma(xr2, xr2, xi2 * xi2));
+  const double yr2 = __builtin_fma(-w.x, di, __builtin_fma(w.y, -dr, sr));
+  const double yi2 = __builtin_fma(w.y, di, __builtin_fma(w.x, -dr, -si));
+  mw = spx_sqrt64_to_f32(0.25 * __builtin_fma(yr2, yr2, yi2 * yi2));
+#endif
+}
 
 #define C5_1 0.30901699437494742
 #define C5_2 (-0.80901699437494742)
@@ -763,27 +785,37 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
       }
       // the next slot's samples (direct) and the untangle factors: on their way while the stores drain
       if (direct) fetch6(s + 4, nx);
-      double2 wu[4];
+      // (two: bins p = lane and lane + 64; bin 240 - p takes the mirror image of bin p's, spx_untangle_mag_pair)
+      double2 wu[2];
 #pragma unroll
-      for (int u = 0; u < 4; u++) wu[u] = lc(SPX_LC_WU + u);
+      for (int u = 0; u < 2; u++) wu[u] = lc(SPX_LC_WU + u);
       wave_sync();
       ASTAMP(1);
-      // untangle the packed transform:  X[k] = E[k] + e^{-2 pi i k/N} O[k]
+      // untangle the packed transform:  X[k] = E[k] + e^{-2 pi i k/N} O[k] -- in conjugate pairs: bins p and 240 - p are made of
+      // the same two points Z[p], Z[240 - p], so one lane reads them once and forms their sums and differences once.  Two passes,
+      // p = lane and lane + 64 up to 120; bins 0 and 120 pair with themselves (a "pair" whose second bin is not stored: the first
+      // is today's sequence on Z[p] twice).  A lane ends the slot with four magnitudes: bins p, 240 - p of either pass.
       float* spec_out = taps.spectrogram ? taps.spectrogram + (size_t)(S.frame_off + j) * 480 : nullptr;
 #pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int k = ln + 64 * u;
-        if (k < 240) {
-          const int k2 = (k == 0) ? 0 : 240 - k;
-          const cplx a = ld(bufB, k), c = ld(bufB, k2);
-          const double b_r = c.r, b_i = -c.i;
-          const float mag = spx_untangle_mag(a.r, a.i, b_r, b_i, wu[u]);
-          hold[u] = mag;
-          if (!keep) mrow[k] = mag;
+      for (int u = 0; u < 2; u++) {
+        const int p = ln + 64 * u;
+        if (p <= 120) {
+          const int q = (p == 0) ? 0 : 240 - p;   // (p = 120: itself)
+          const bool two = p > 0 && p < 120;
+          const cplx a = ld(bufB, p), c = ld(bufB, q);
+          float mp, mq;
+          spx_untangle_mag_pair(a.r, a.i, c.r, c.i, wu[u], mp, mq);
+          hold[2 * u] = mp;
+          hold[2 * u + 1] = mq;
+          if (!keep) {
+            mrow[p] = mp;
+            if (two) mrow[q] = mq;
+          }
           if (spec_out) {
-            spec_out[k] = mag;
-            if (k > 0) spec_out[480 - k] = mag;
+            spec_out[p] = mp;
+            if (p > 0) spec_out[480 - p] = mp;
             else spec_out[240] = (float)__builtin_fabs(a.r - a.i);
+            if (two) { spec_out[q] = mq; spec_out[480 - q] = mq; }
           }
         }
       }
@@ -795,9 +827,12 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
     {
       float* mrow = mags + (size_t)(wave == 0 ? TF : TF - 4 + wave) * MS;
 #pragma unroll
-      for (int u = 0; u < 4; u++) {
-        const int k = lane + 64 * u;
-        if (k < 240) mrow[k] = hold[u];
+      for (int u = 0; u < 2; u++) {
+        const int p = lane + 64 * u;
+        if (p <= 120) {
+          mrow[p] = hold[2 * u];
+          if (p > 0 && p < 120) mrow[240 - p] = hold[2 * u + 1];
+        }
       }
     }
   } else if constexpr (WCT == 240) {

@@ -1,6 +1,8 @@
 // Plans (include/speedy_hip.h spx_plan_*): the constant tables of one (sample rate, hysteresis mode) -- the DFT spec's twiddles
 // (spx_twiddle.h: machine-independent), the Hamming window, the hysteresis tapers, Rader's tables for a prime window -- and the
 // sizes and capacities derived from the rate.  Reference: speedy.c:206-299 (speedyCreateStream), speedy.h:136-146.
+#include <string.h>
+
 #include "spx_engine.h"
 #include "spx_twiddle.h"
 #include "spx_twiddle_hashes.h"
@@ -219,6 +221,17 @@ spx_plan_t spx_plan_create(int sample_rate, int match_matlab) {
           return nullptr;
         }
   }
+  // spx_analysis_kernel<16, 240> untangles bins p and W - p in one lane from ONE factor (spx_untangle_mag_pair): tw2[W - p] must
+  // be (-x, +y) of tw2[p] = (x, y) bit for bit, p = 1 .. W/2 - 1 (tests/test_untangle_table.py states the same on the CPU)
+  if (lane_tab)
+    for (int q = 1; q < W / 2; q++) {
+      const double mx = -tw2[2 * q], my = tw2[2 * q + 1];
+      if (memcmp(&mx, &tw2[2 * (W - q)], sizeof mx) != 0 || memcmp(&my, &tw2[2 * (W - q) + 1], sizeof my) != 0) {
+        delete p;
+        fail(-1, "spx_plan_create: the untangle table is not conjugate-symmetric bit for bit (tw2[W - p] != (-x, +y) of tw2[p])");
+        return nullptr;
+      }
+    }
   for (int i = 0; i <= d.F; i++) tf[i] = (d.F - i) / (float)d.F;    // speedy.c:597
   for (int i = 0; i <= d.Pp; i++) tp[i] = (d.Pp - i) / (float)d.Pp;  // speedy.c:604
   {

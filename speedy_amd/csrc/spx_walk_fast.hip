@@ -47,6 +47,9 @@
 #ifndef SPX_WALK_PRIO
 #define SPX_WALK_PRIO 3  // the search waves are the latency-critical chain: they issue first where another kernel shares a SIMD
 #endif
+// (Also in the pipelined order, where a walk launch has three steps to finish in and the step waits for the analysis kernel: with
+// the analysis waves above these the lean walk launch went 1.79 -> 2.50 ms and the step 0.81 -> 0.885 ms, with both at 0 the step
+// lost 2 % -- profiles/analysis_first.txt, DESIGN.md 10.  The chain pays every lost issue slot in full.)
 // LDS bank placement of the shifted copies relative to the originals (bytes added between the two): lanes of adjacent lags
 // read alternately from a signal and from its shifted copy, so the copies' bank offset decides the conflicts.
 #ifndef SPX_PAD_MONO
