@@ -299,6 +299,56 @@ int spx_edit_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, 
                     const int64_t* n_ops, const int64_t* n_out, const int32_t* index, const int64_t* q_off, const int64_t* q,
                     int64_t* r, int32_t* rec, int inverse, void* hip_stream);
 
+/* ---- EDIT LIST, SCALED: replay on tracks at a higher sample rate, int16 or float ----
+ * The most common companion of a key is the master it was made from: a 44.1 or 48 kHz stereo float mix beside the 16 kHz mono track
+ * the analysis wants.  spx_edit_replay_scaled is spx_edit_replay for such a track: speed and pitch are decided once, at the key's
+ * rate, and the master is cut in the same places -- the cheap run plus one pass over the master's bytes (profiles/edit_scaled.txt).
+ * tests/edit_scaled_ref.py states the definition below in Python integers.
+ *
+ * p / q is the master's rate over the key's (3/1, 2/1, 441/160, 320/147, 1/1 ...).  The library reduces it by its gcd and requires
+ * 1 <= q <= p <= 32 q and p <= 32768 after the reduction.  S(x) = floor(x p / q); spx_edit_scale returns it on the host (-1 for a
+ * ratio that is refused or x < 0).
+ *
+ * For stream i, with L as in spx_edit_replay: no = min(n_out[i], jobs[i].out_cap), N' = S(no), L' = min(S(L), tracks[i].n_in).
+ * Record (out_at, a, b, n) covers master frames [S(out_at), S(out_at + n)), cut at N':
+ *   n' = S(out_at + n) - S(out_at) -- at least 1 because p >= q: the extents tile [0, N') --, a' = S(a), b' = S(b), and output
+ *   frame o of the record has t = o - S(out_at).  A source frame at or behind L' reads as 0 (+0.0f).
+ *   copy                  y[a' + t]
+ *   cross-fade, int16     (y[a' + t] * (n' - t) + y[b' + t] * t) / n', truncated toward zero; exact for every n' <= 65535 (the ratio
+ *                         cap keeps every list the walk kernel writes far inside that)
+ *   cross-fade, float     ((ya * (float)(n' - t)) + (yb * (float)t)) / (float)n': every operation rounded to float, no fused
+ *                         multiply-add, the division correctly rounded; non-finite inputs give what IEEE arithmetic gives
+ * At a non-integer ratio a' and b' are floored SEPARATELY, so the two ramps of a cross-fade can sit up to one master frame off the
+ * exact ratio; at integer ratios the positions are exact.  At p == q with int16 the output is spx_edit_replay's, byte for byte.
+ *
+ *   jobs, ops, ops_cap, n_ops, n_out   exactly what spx_edit_replay takes (n_ops, n_out: DEVICE -- nothing comes back to the host)
+ *   tracks   HOST   one per stream: in_off / out_off in ELEMENTS of the sample format from y_in / y_out; n_in / out_cap the track's
+ *            own length and output capacity in frames at the master's rate; channels in 1 .. 65535
+ *   sample_format   SPX_SAMPLES_INT16 (y_in, y_out: int16_t) or SPX_SAMPLES_FLOAT (float)
+ *   y_in     DEVICE read only inside [0, L') of each track
+ *   y_out    DEVICE nothing is written outside a stream's N' frames
+ *   n_out_y  DEVICE int64[n_streams], written by the call:
+ *              N'    the stream was rendered, N' frames
+ *              -N'   N' > tracks[i].out_cap: nothing written for that stream
+ *              0     n_out[i] <= 0, n_ops[i] <= 0 or n_ops[i] > ops_cap[i]: nothing written
+ * No stream disturbs another; whatever the records hold, nothing is read outside [0, L') of a track or outside the stream's region
+ * of ops.  Refused with -1 and spx_last_error before anything is enqueued, the outputs and the plan untouched: everything
+ * spx_edit_replay refuses; a ratio outside the rule; an unknown sample_format; a NULL n_out_y; a negative n_in or out_cap; y_in or
+ * y_out not aligned to the sample size; a stream with S(min(jobs[i].out_cap, 2^31 - 1)) or S(L) above 2^31 - 1 (master positions
+ * fit int32 inside the kernel, as the key's do in spx_edit_replay's).
+ * COST: one pass over the master's bytes, spx_edit_replay's kernel shape with the records scaled once per block.
+ * OUT OF SCOPE: p < q (label or feature tracks below the key's rate: they need record compaction); resampling the master down to
+ * the key, which stays the caller's job; lookups in master frames (scale the queries of spx_edit_lookup with spx_edit_scale); the
+ * pipeline object. */
+#define SPX_SAMPLES_INT16 0
+#define SPX_SAMPLES_FLOAT 1
+typedef struct { int64_t in_off, out_off, n_in, out_cap; int32_t channels, reserved; } spx_edit_master;
+int64_t spx_edit_scale(int64_t x, int32_t p, int32_t q);
+int spx_edit_replay_scaled(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const spx_edit_op* ops,
+                           const int64_t* ops_cap, const int64_t* n_ops, const int64_t* n_out, const spx_edit_master* tracks,
+                           int32_t p, int32_t q, int sample_format, const void* y_in, void* y_out, int64_t* n_out_y,
+                           void* hip_stream);
+
 /* ---- BATCH DTW: align pairs of feature sequences on the device -- cost, warp path and slopes per pair ----
  * The reference's perceptual check (TestSpeechSample, sonic_test.cc:639-724) aligns the spectrogram of the output to that of the
  * input by dynamic time warping (dynamic_time_warping.{h,cc}) and asks whether the warp path has the slope the speed promised.
@@ -720,6 +770,8 @@ int spx_debug_last_lookup_grid(int* launches);
 int spx_debug_last_replay_grid(int* launches);
 /* ... and the query blocks per stream of the last spx_edit_lookup (4 .. 1 024, chosen as spx_map_lookup chooses them), with its launches. */
 int spx_debug_last_edit_lookup_grid(int* launches);
+/* ... and the output blocks per stream of the last spx_edit_replay_scaled (4 096 values each, int16 or float), with its launches. */
+int spx_debug_last_scaled_grid(int* launches);
 /* ... and the workgroups of the last spx_batch_dtw: one per pair, in each of its two launches (*launches = 2). */
 int spx_debug_last_dtw_grid(int* launches);
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls);

@@ -26,6 +26,11 @@ class EditTrack(C.Structure):  # spx_edit_track
     _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("channels", C.c_int32), ("reserved", C.c_int32)]
 
 
+class EditMaster(C.Structure):  # spx_edit_master
+    _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("n_in", C.c_int64), ("out_cap", C.c_int64),
+                ("channels", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DtwJob(C.Structure):  # spx_dtw_job
     _fields_ = [("a_off", C.c_int64), ("b_off", C.c_int64), ("path_off", C.c_int64), ("n_a", C.c_int32), ("n_b", C.c_int32)]
 
@@ -71,6 +76,10 @@ SYMBOLS = {
     "spx_edit_index": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spx_edit_lookup": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "spx_edit_scale": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "spx_edit_replay_scaled": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(EditMaster), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "spx_dtw_workspace_bytes": (C.c_size_t, [C.POINTER(DtwJob), C.c_int, C.c_int]),
     "spx_batch_dtw": (C.c_int, [C.c_void_p, C.POINTER(DtwJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -116,6 +125,7 @@ SYMBOLS = {
     "spx_debug_last_lookup_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_debug_last_replay_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_debug_last_edit_lookup_grid": (C.c_int, [C.POINTER(C.c_int)]),
+    "spx_debug_last_scaled_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_timing_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "spx_timing_last_tension_ms": (C.c_double, []),
     "spx_timing_last_rate_ms": (C.c_double, []),

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import EditTrack, StreamJob, Taps, lib
+from ._lib import EditMaster, EditTrack, StreamJob, Taps, lib
 
 
 class Plan:
@@ -54,7 +54,8 @@ class Batch:
     run_ahead.
     edits: run() is spx_batch_run_edits -- the same outputs, counts and taps, and the jobs' edit lists beside them: edits(i) returns
     stream i's records (out_at, a, b, n), replay(tracks, channels) applies the lists to companion tracks of the same lengths on the
-    GPU (spx_edit_replay).  The capacities are spx_plan_edit_ops' (ops_caps: one value or one per stream instead); not together
+    GPU (spx_edit_replay), replay_scaled(tracks, channels, ratio) to masters at a higher sample rate, int16 or float32
+    (spx_edit_replay_scaled).  The capacities are spx_plan_edit_ops' (ops_caps: one value or one per stream instead); not together
     with rate or time_map.  The plain call only.  locate(i, positions) and locate_all(positions) convert positions through the lists
     to the sample (spx_edit_lookup), where lookup answers to 10 ms."""
 
@@ -368,6 +369,52 @@ class Batch:
         nout = self.d_nout.cpu().numpy()
         out = d_yout.cpu().numpy()
         return [out[tr[i].out_off:tr[i].out_off + max(0, int(nout[i])) * int(ch[i])].copy() for i in range(self.n)]
+
+    def replay_scaled(self, tracks, channels, ratio, stream=None):
+        """spx_edit_replay_scaled over the whole batch: tracks[i] = the master of stream i at ratio = (p, q) (or an int) times the
+        key's sample rate -- numpy or torch, int16 or float32, one dtype per call, interleaved, any length (size // channels frames
+        count); channels = its channel count (one value or one per stream).  The output capacity of stream i is out_caps[i] scaled
+        by the ratio.  Returns the rendered masters (host numpy of the tracks' dtype), trimmed to the counts the call wrote."""
+        if not self.with_edits:
+            raise RuntimeError("the batch was made without edits=True")
+        assert len(tracks) == self.n
+        p, q = (int(ratio), 1) if isinstance(ratio, (int, np.integer)) else (int(ratio[0]), int(ratio[1]))
+        ys = [np.ascontiguousarray(y.detach().cpu().numpy() if torch.is_tensor(y) else y).ravel() for y in tracks]
+        kinds = {y.dtype for y in ys}
+        if len(kinds) != 1 or next(iter(kinds)) not in (np.dtype(np.int16), np.dtype(np.float32)):
+            raise ValueError("the tracks of one call are all int16 or all float32, not %s" % sorted(str(k) for k in kinds))
+        dtype = next(iter(kinds))
+        fmt = 1 if dtype == np.dtype(np.float32) else 0        # SPX_SAMPLES_FLOAT / SPX_SAMPLES_INT16
+        L = self.plan.L
+        ch = np.broadcast_to(np.asarray(channels, np.int32), (self.n,))
+        tr = (EditMaster * self.n)()
+        in_off = out_off = 0
+        for i in range(self.n):
+            cap = L.spx_edit_scale(int(self.out_caps[i]), p, q)
+            if cap < 0:
+                raise RuntimeError("spx_edit_scale refuses the ratio %d / %d" % (p, q))
+            t = tr[i]
+            t.in_off, t.out_off, t.channels, t.reserved = in_off, out_off, int(ch[i]), 0
+            t.n_in, t.out_cap = ys[i].size // max(1, int(ch[i])), cap
+            in_off += ys[i].size
+            out_off += cap * int(ch[i])
+        host = np.zeros(max(1, in_off), dtype)
+        for i, y in enumerate(ys):
+            host[tr[i].in_off:tr[i].in_off + y.size] = y
+        d_y = torch.from_numpy(host).to(self.device)
+        d_yout = torch.zeros(max(1, out_off), dtype=d_y.dtype, device=self.device)
+        d_count = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        rc = L.spx_edit_replay_scaled(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
+                                      self.d_nout.data_ptr(), tr, p, q, fmt, d_y.data_ptr(), d_yout.data_ptr(), d_count.data_ptr(), hs)
+        if rc != 0:
+            raise RuntimeError("spx_edit_replay_scaled: " + L.spx_last_error().decode())
+        torch.cuda.synchronize(self.device)
+        count = d_count.cpu().numpy()
+        if (count < 0).any():
+            raise RuntimeError("output capacity exceeded for streams %s" % np.nonzero(count < 0)[0][:8])
+        out = d_yout.cpu().numpy()
+        return [out[tr[i].out_off:tr[i].out_off + int(count[i]) * int(ch[i])].copy() for i in range(self.n)]
 
     def locate_all(self, positions, inverse=False, records=False, stream=None):
         """spx_edit_lookup over the whole batch, to the sample: positions[i] = stream i's queries (any int sequence, may be empty).
