@@ -201,7 +201,42 @@ def test_planted_lists(fmt, p, q):
         plan.close()
 
 
-# ------------------------------------------------------------------ counts ------------------------------------------------------------------
+def test_planted_lists_at_one_to_one_through_both_calls():
+    """The first three planted lists on mono int16 tracks through spx_edit_replay and through spx_edit_replay_scaled at 1 / 1 -- two
+    instantiations of one kernel body (identity and multiply).  At 1 / 1 a block of 4096 values holds about 2 700 of list 0's
+    records, so both kernels read them where they lie (the recorded lists of the equality test above always stage); list 1's
+    cross-fade straddles no block here but its one-frame cross-fade and the odd offsets exercise the head and tail stores; list 2 is
+    the n = 21 845 cross-fade.  The two output buffers are the same bytes, guard values included, each equals the definition, and
+    the counts are n_out."""
+    import torch
+    from speedy_amd._lib import EditTrack
+    from speedy_amd.batch import Plan
+    lists = _planted_lists()[:3]
+    assert sum(1 for r in lists[0][1] if r[0] < 4096) > 512
+    plan = Plan(16000, False)
+    try:
+        b = _planted(plan, lists)
+        tracks = [U.track("int16", l[0], 950 + i) for i, l in enumerate(lists)]
+        r = U.Scaled(b, [1, 1, 1], 1, 1, "int16", tracks, in_res=(7, 1, 3), out_res=(1, 7, 3))
+        rc, msg = r.call()
+        assert rc == 0, msg
+        old = (EditTrack * b.n)()
+        for i in range(b.n):
+            old[i].in_off, old[i].out_off, old[i].channels, old[i].reserved = r.tr[i].in_off, r.tr[i].out_off, 1, 0
+        d_old = torch.full((r.size_out,), U.CANARY16, dtype=torch.int16, device=b.device)
+        L = plan.L
+        rc = L.spx_edit_replay(plan.h, b.jobs, b.n, b.d_ops.data_ptr(), b._ops_cap_ptr(), b.d_nops.data_ptr(), b.d_nout.data_ptr(), old,
+                               r.d_y.data_ptr(), d_old.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, L.spx_last_error()
+        assert _sync_np(d_old).tobytes() == r.out().tobytes()
+        assert r.counts().tolist() == [l[2] for l in lists]
+        want = [SC.replay_scaled_np(l[1], y, 1, l[0], l[2], 1, 1, l[0], "int16") for l, y in zip(lists, tracks)]
+        r.check(want)                                   # (and so does the plain call's buffer: it is the same bytes)
+    finally:
+        plan.close()
+
+
+# ------------------------------------------------------------------ counts------------------------------------------------------------------
 
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_counts_of_streams_that_do_not_fit_or_have_nothing(key, fmt):

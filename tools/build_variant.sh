@@ -11,8 +11,13 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-ma
 HOT=${SPX_HOT_SCHED:--mllvm -amdgpu-sched-strategy=max-memory-clause}
 OD=../lib/obj
 /opt/rocm/bin/hipcc $FLAGS $HOT $EXTRA -c spx_hot.hip -o ../lib/obj/spx_hot_$NAME.o
+# every other object in the Makefile's own order, read from its SRC line (a list kept here went stale once)
 OBJ=""
-for o in spx_walk spx_plan spx_engine spx_mixed spx_diag spx_pipeline sonic2_api speedy_api spx_rate sonic2_pool wave_compat spx_rate_batch spx_convert spx_select_check spx_map spx_tension_seq spx_dtw spx_edits spx_edit_lookup spx_twopass; do OBJ="$OBJ $OD/$o.o"; done
+for s in $(sed -n 's/^SRC ?= *//p' Makefile); do
+  o=${s%.*}
+  [ "$o" = spx_hot ] || OBJ="$OBJ $OD/$o.o"
+done
+[ -n "$OBJ" ] || { echo "tools/build_variant.sh: no SRC line in speedy_amd/csrc/Makefile" >&2; exit 1; }
 /opt/rocm/bin/hipcc $FLAGS -shared -o ../lib/ab/libspeedy_hip_$NAME.so ../lib/obj/spx_hot_$NAME.o $OBJ
 rm -f ../lib/obj/spx_hot_$NAME.o
 echo "built speedy_amd/lib/ab/libspeedy_hip_$NAME.so"

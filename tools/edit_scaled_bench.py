@@ -16,6 +16,11 @@ Workload: 256 streams x 10 s, 16 kHz mono, 3.5x nonlinear (bench.py's own inputs
         6  ONE spx_batch_run of 256 x 10 s as a 48 kHz stereo job (bench.py's inputs for that rate) against one spx_batch_run_edits
            at 16 kHz plus (4): what deciding on the key and rendering the master costs beside walking the master itself
 
+  python tools/edit_scaled_bench.py ab NAME...
+        `replay` in a fresh process per build under `timeout`, two rounds interleaved: the shipped library, then
+        speedy_amd/lib/ab/libspeedy_hip_<NAME>.so for every NAME (tools/build_variant.sh's place), selected through SPEEDY_HIP_LIB as
+        tools/edit_list_time.py ab does; rows (1) to (4) of each, and nothing more after a process that fails
+
 The timing is tools/edit_list_time.py's (30 calls back to back after 5, HIP events on the stream)."""
 import os
 import statistics
@@ -177,6 +182,22 @@ def master_step():
     plan.close()
 
 
+def ab(names):
+    for r in (1, 2):
+        for v in ["shipped"] + names:
+            env = dict(os.environ)
+            env.pop("SPEEDY_HIP_LIB", None)
+            if v != "shipped":
+                env["SPEEDY_HIP_LIB"] = os.path.join(ROOT, "speedy_amd", "lib", "ab", "libspeedy_hip_%s.so" % v)
+            out = subprocess.run(["timeout", "-k", "10", str(STEP_TIMEOUT_S["replay"]), sys.executable, os.path.abspath(__file__), "replay"],
+                                 env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            if out.returncode != 0:
+                sys.exit("pass %d, %s: exit status %d, nothing more is started\n%s" % (r, v, out.returncode, out.stdout[-2000:]))
+            for l in out.stdout.splitlines():
+                if l.startswith(("1 / 1", "(1)", "(2)", "(3)", "(4)", "medians")):
+                    print("pass %d  %-8s %s" % (r, v, l), flush=True)
+
+
 def driver(out_path):
     with open(out_path, "a") as f:
         f.write("run of %s\n" % time.strftime("%Y-%m-%d %H:%M:%S"))
@@ -200,6 +221,8 @@ if __name__ == "__main__":
         import torch
         assert torch.cuda.is_available(), "needs an MI355X"
         replay_step() if args[0] == "replay" else master_step()
+    elif len(args) >= 2 and args[0] == "ab":
+        ab(args[1:])
     elif not args or (len(args) == 2 and args[0] == "--out"):
         driver(args[1] if args else os.path.join(ROOT, "profiles", "edit_scaled.txt"))
     else:
