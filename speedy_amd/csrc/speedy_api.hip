@@ -11,6 +11,7 @@
 
 #include "../../include/speedy.h"
 #include "spx_internal.h"
+#include "spx_frame_math.h"
 #include "spx_log.h"
 
 extern "C" const char* speedyHipLastError(void);
@@ -183,20 +184,20 @@ __device__ inline float hk_slot(const SpxPlanDev& P, const float* scr, int64_t o
   const int64_t j = tau - time0;
   return (j >= origin && j < origin + cap && j >= 0) ? scr[4 * (j - origin) + 0] : 0.0f;
 }
+// The hk_* kernels below run single statements of the feature chain for the unit-level calls: each statement is the function of
+// spx_frame_math.h that the tension kernels compile.
 __device__ inline float hk_hysteresis(const SpxPlanDev& P, const float* scr, int64_t origin, int64_t cap, int64_t time0, int64_t hi,
                                       int64_t k) {
   float future_max = 0.0f, past_max = 0.0f;
   for (int i = 0; i <= P.F; i++) {   // speedy.c:594-608
-    float v = hk_slot(P, scr, origin, cap, time0, hi, k + i);
-    v *= P.taperF[i];
+    const float v = spx_fm_hysteresis_tap(hk_slot(P, scr, origin, cap, time0, hi, k + i), P.taperF[i]);
     if (v > future_max) future_max = v;
   }
   for (int i = 0; i <= P.Pp; i++) {
-    float v = hk_slot(P, scr, origin, cap, time0, hi, k - i);
-    v *= P.taperP[i];
+    const float v = spx_fm_hysteresis_tap(hk_slot(P, scr, origin, cap, time0, hi, k - i), P.taperP[i]);
     if (v > past_max) past_max = v;
   }
-  return (float)((double)(past_max + future_max) / 2.0);   // speedy.c:609
+  return spx_fm_hysteresis(past_max, future_max);
 }
 __global__ void hk_hysteresis_kernel(SpxPlanDev P, const float* scr, int64_t origin, int64_t cap, int64_t time0, int64_t hi, int64_t k,
                                      float* out) {
@@ -207,10 +208,10 @@ __global__ void hk_hysteresis_kernel(SpxPlanDev P, const float* scr, int64_t ori
 // its argument, speedy.c:515): energy low-pass iterated once more, local energy, compression, hysteresis slot of `at_time`
 __global__ void hk_local_energy_kernel(SpxPlanDev P, SpxStreamState* st, float energy, float* slot, float* feat) {
   if (threadIdx.x != 0) return;
-  const float lp = P.one_minus_alpha * energy + P.alpha * st->lp;   // speedy.c:74
+  const float lp = spx_fm_lowpass(P.one_minus_alpha, P.alpha, energy, st->lp);
   st->lp = lp;
-  const float local = energy / lp;
-  const float comp = (float)__builtin_sqrt(local > 2 ? 2.0 : (double)local);
+  const float local = spx_fm_local_energy(energy, lp);
+  const float comp = spx_fm_compress(local);
   *slot = comp;
   if (feat) { feat[1] = lp; feat[2] = local; feat[3] = comp; }
 }
@@ -229,12 +230,12 @@ __global__ void hk_spectral_difference_kernel(SpxPlanDev P, SpxStreamState* st, 
   const float inv = (float)(1.0 / (__builtin_sqrt((double)e) + (double)eps));     // speedy.c:642
   const float inv2 = (float)(1.0 / (__builtin_sqrt((double)e2) + (double)eps));
   for (int i = 0; i < W; i++) { norm_row[i] = cur[i] * inv; norm_last[i] = last[i] * inv2; }
-  const float lowthr = (float)(0.04 * (double)1.41421f);               // speedy.c:682
+  const float lowthr = SPX_FM_LOW_THRESHOLD;
   int first_k = st->tension_first;
   const bool first_call = first_k < 0;
   if (first_call) { first_k = (int)k; st->tension_first = first_k; }  // the very first call is skipped (speedy.c:293,691)
   // any_order: a time asked again (or out of order) -- only the FIRST call ever is the skipped one, whatever its time
-  const bool low = e <= lowthr || (any_order ? first_call : (int)k == first_k);
+  const bool low = spx_fm_low_energy(e) || (any_order ? first_call : (int)k == first_k);
   float lsd = 0.0f, ewld = 0.0f, rel = 0.0f, sc = 0.0f;
   if (!low) {
     const float thr = (float)((double)mx / 100.0);                     // speedy.c:709
@@ -246,19 +247,18 @@ __global__ void hk_spectral_difference_kernel(SpxPlanDev P, SpxStreamState* st, 
       }
       lsd = (float)((double)lsd + term);                               // float +=
     }
-    ewld = lsd * hyst;                                                 // speedy.c:720
+    ewld = spx_fm_weighted(lsd, hyst);
   }
-  const float lpf = P.one_minus_alpha * ewld + P.alpha * st->lpf;      // the difference filter runs on skipped frames too (0)
+  const float lpf = spx_fm_lowpass(P.one_minus_alpha, P.alpha, ewld, st->lpf);   // the difference filter runs on skipped frames too (0)
   st->lpf = lpf;
   if (!low) {
-    rel = (float)((double)ewld / ((double)lpf + 0.01 * (double)123.979f));         // speedy.c:725-726
-    sc = (float)fmin((double)rel, (double)(4 * 0.971975f));                        // speedy.c:727-728
+    rel = spx_fm_relative(ewld, lpf);
+    sc = spx_fm_clamp(rel);
   }
   feat[0] = e; feat[4] = hyst; feat[5] = low ? 1.0f : 0.0f; feat[6] = lsd; feat[7] = ewld; feat[8] = lpf; feat[9] = rel;
   feat[10] = sc; feat[13] = (float)k; feat[14] = lowthr;
   if (tension_out) {
-    const float a = 0.5f, b = 0.25f, M_E_ = 0.7f, M_S = 1.0f;
-    const float tension = a * (hyst - M_E_) + b * (sc - M_S);          // speedy.c:761
+    const float tension = spx_fm_tension(hyst, sc);
     feat[11] = tension;
     *tension_out = tension;
   }
@@ -420,7 +420,7 @@ float speedyComputeSpeedFromTension(float tension, float R_g, float fb, speedySt
   if (!s->started) {  // the state record is initialised by the first launch; before it, do that here
     SpxStreamState z;
     memset(&z, 0, sizeof(z));
-    z.lp = 2.14204f; z.lpf = 123.837f;  // speedy.c:263-264
+    z.lp = SPX_FM_ENERGY_LP0; z.lpf = SPX_FM_DIFFERENCE_LP0;
     z.tension_first = -1;
     (void)hipMemcpyAsync(s->dState, &z, sizeof(z), hipMemcpyHostToDevice, s->hs);
     (void)hipStreamSynchronize(s->hs);
@@ -507,7 +507,7 @@ static void hook_ensure_state(speedyStream s) {
   if (s->started) return;   // the state record is initialised by the first launch; before it, do that here
   SpxStreamState z;
   memset(&z, 0, sizeof(z));
-  z.lp = 2.14204f; z.lpf = 123.837f;  // speedy.c:263-264
+  z.lp = SPX_FM_ENERGY_LP0; z.lpf = SPX_FM_DIFFERENCE_LP0;
   z.tension_first = -1;
   (void)hipMemcpyAsync(s->dState, &z, sizeof(z), hipMemcpyHostToDevice, s->hs);
   (void)hipStreamSynchronize(s->hs);

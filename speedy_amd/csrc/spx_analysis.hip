@@ -16,6 +16,7 @@
 #include <stdlib.h>
 
 #include "spx_internal.h"
+#include "spx_frame_math.h"    // SPX_FM_LOW_THRESHOLD
 #include "spx_walk_common.h"   // wave_max_f (the DPP reduction of non-negative floats as unsigned integers)
 
 #ifndef SPX_TF
@@ -1549,7 +1550,7 @@ spx_analysis_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, int 
     return term;
   };
   auto write_rec = [&](int f, float lsd) {
-    const float lowthr = (float)(0.04 * (double)1.41421f);                     // speedy.c:682
+    const float lowthr = SPX_FM_LOW_THRESHOLD;                                 // speedy.c:682, spx_frame_math.h
     const float e = fE[f + 1];
     SpxFrameRec r;
     r.energy = e;

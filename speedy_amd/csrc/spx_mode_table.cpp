@@ -1,8 +1,10 @@
 // Host-only build of the launch-mode decision (spx_mode.h) for tests/test_mode_table.py, of the job rules (spx_jobs.h) for
-// tests/test_job_rules.py and of the two-pass call's speed formula (spx_twopass.h) for tests/test_twopass_abi.py: plain g++, no HIP.  The mode query and its answer are flat arrays of 64-bit integers so that the Python
+// tests/test_job_rules.py, of the two-pass call's speed formula (spx_twopass.h) for tests/test_twopass_abi.py and of the frame-rate
+// feature chain (spx_frame_math.h) for tests/test_frame_math.py: plain g++ (-ffp-contract=off: no fused multiply-add), no HIP.  The mode query and its answer are flat arrays of 64-bit integers so that the Python
 // side mirrors them by NAME (the two name lists below are exported).
 #include <string.h>
 
+#include "spx_frame_math.h"
 #include "spx_jobs.h"
 #include "spx_mode.h"
 #include "spx_twopass.h"
@@ -124,5 +126,57 @@ const char* spx_mode_table_job_fault_text(int code) {
 // spx_twopass_speed: the second-pass speed the retarget kernel writes for one stream (the same text, compiled for the host)
 float spx_mode_table_twopass_speed(double want, int length_mode, long long n_in, long long n_probe) {
   return spx_twopass_speed(want, length_mode, n_in, n_probe);
+}
+
+// spx_frame_math.h stage by stage over n rows: out[i] = stage(inputs[i]), the text the kernels compile
+void spx_frame_math_lowpass(int n, float one_minus_alpha, float alpha, const float* x, const float* y, float* out) {
+  for (int i = 0; i < n; i++) out[i] = spx_fm_lowpass(one_minus_alpha, alpha, x[i], y[i]);
+}
+void spx_frame_math_local_energy(int n, const float* e, const float* l, float* out) {
+  for (int i = 0; i < n; i++) out[i] = spx_fm_local_energy(e[i], l[i]);
+}
+void spx_frame_math_compress(int n, const float* local, float* out) {
+  for (int i = 0; i < n; i++) out[i] = spx_fm_compress(local[i]);
+}
+// one tapered maximum over taps c[0 .. n) with weights taper[0 .. n), and the half-sum of two
+float spx_frame_math_tapered_max(int n, const float* c, const float* taper) {
+  float m = 0.0f;
+  for (int i = 0; i < n; i++) {
+    const float v = spx_fm_hysteresis_tap(c[i], taper[i]);
+    if (v > m) m = v;
+  }
+  return m;
+}
+float spx_frame_math_hysteresis(float past_max, float future_max) { return spx_fm_hysteresis(past_max, future_max); }
+// the low gate of tension frames k0 .. k0 + n, as the kernels write it
+void spx_frame_math_low(int n, const float* e, int k0, int first_k, float* out) {
+  for (int i = 0; i < n; i++) out[i] = (spx_fm_low_energy(e[i]) || k0 + i == first_k) ? 1.0f : 0.0f;
+}
+float spx_frame_math_low_threshold(void) { return SPX_FM_LOW_THRESHOLD; }
+void spx_frame_math_start_values(float* lp_lpf) { lp_lpf[0] = SPX_FM_ENERGY_LP0; lp_lpf[1] = SPX_FM_DIFFERENCE_LP0; }
+void spx_frame_math_weighted(int n, const float* lsd, const float* hyst, float* out) {
+  for (int i = 0; i < n; i++) out[i] = spx_fm_weighted(lsd[i], hyst[i]);
+}
+void spx_frame_math_relative(int n, const float* ewld, const float* l, float* out) {
+  for (int i = 0; i < n; i++) out[i] = spx_fm_relative(ewld[i], l[i]);
+}
+void spx_frame_math_clamp(int n, const float* rel, float* out) {
+  for (int i = 0; i < n; i++) out[i] = spx_fm_clamp(rel[i]);
+}
+void spx_frame_math_tension(int n, const float* hyst, const float* sc, float* out) {
+  for (int i = 0; i < n; i++) out[i] = spx_fm_tension(hyst[i], sc[i]);
+}
+// the speed stage over n tensions in sequence, durations[2] = {cur_dur, des_dur} carried in and out: the statements of
+// spx_speed_kernel and of the kernels' closed-loop pass, then the blend
+void spx_frame_math_speed(int n, const float* tension, float Rg, float nl, float fb, float* durations, float* out) {
+  float cur_dur = durations[0], des_dur = durations[1];
+  for (int i = 0; i < n; i++) {
+    float req = spx_fm_raw_speed(Rg, tension[i]);
+    if (fb > 0) req = spx_fm_feedback(req, fb, cur_dur, des_dur);
+    cur_dur = spx_fm_advance(cur_dur, req);
+    des_dur = spx_fm_advance(des_dur, Rg);
+    out[i] = spx_fm_blend(req, nl, Rg);
+  }
+  durations[0] = cur_dur; durations[1] = des_dur;
 }
 }

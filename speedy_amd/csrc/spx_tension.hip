@@ -8,6 +8,8 @@
 //                                                         speedy.c:682-700,720-728
 //   a7  tension                                           speedy.c:752-766
 //   a9  speed from tension (+ duration feedback), blend   speedy.c:768-788, soniclib.c:339-345
+// Each statement of that chain is a function of spx_frame_math.h (with its line in the reference): the one text that this
+// kernel, spx_tension_seq_kernel and the unit-level API's kernels compile.
 // Output: scratch[4*k + 3] = the speed the shim sets before handing ring buffer k to the time-scale stage
 // (soniclib.c:354), plus the tension / speed / features taps.
 //
@@ -17,6 +19,7 @@
 // tension frames whose speeds are final (`speed_ready`), which the walk kernel polls.  The walk workgroups -- the
 // latency-critical chain of the whole job -- then never execute a frame-rate pass themselves.
 #include "spx_internal.h"
+#include "spx_frame_math.h"
 
 #define SPX_CH 512   // frames per pass chunk held in LDS
 // Frames per chunk when the analysis kernel runs concurrently (a multiple of the 16-frame tile).  Measured on the
@@ -27,7 +30,7 @@
 #endif
 #define SPX_TENSION_THREADS 256
 
-// y[i] = a*x[i] + b*y[i-1] for i < n in the reference's rounding order (float product, float product, float sum --
+// y[i] = a*x[i] + b*y[i-1] for i < n in the reference's rounding order (spx_fm_lowpass_input, spx_fm_lowpass_step --
 // the recurrence cannot be re-associated), x in sA, y to sB.  Run by the 64 lanes of wave 0: 64 products a*x[i] are
 // formed in parallel, then the chain runs on uniform values with a v_readlane per element -- two dependent VALU
 // operations per element instead of an LDS round trip.  Returns the last y.
@@ -35,7 +38,7 @@ __device__ __forceinline__ float iir_wave(const float* sA, float* sB, int n, flo
   const int lane = threadIdx.x;
   for (int b0 = 0; b0 < n; b0 += 64) {
     const int m = n - b0 < 64 ? n - b0 : 64;
-    const float ax = a * ((lane < m) ? sA[b0 + lane] : 0.0f);
+    const float ax = spx_fm_lowpass_input(a, (lane < m) ? sA[b0 + lane] : 0.0f);
     if (m == 64) {
       // A full block: the chain runs on lane 0 alone -- per element one v_readlane (it ignores EXEC), the two dependent
       // operations and one LDS store at a constant offset; no per-element bound check, no lane masks.  (Before: ten
@@ -44,7 +47,7 @@ __device__ __forceinline__ float iir_wave(const float* sA, float* sB, int n, flo
 #pragma unroll
         for (int j = 0; j < 64; j++) {
           const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ax), j));
-          y = s + b * y;
+          y = spx_fm_lowpass_step(s, b, y);
           sB[b0 + j] = y;
         }
       }
@@ -58,7 +61,7 @@ __device__ __forceinline__ float iir_wave(const float* sA, float* sB, int n, flo
       for (int j = 0; j < 64; j++) {
         if (j < m) {  // uniform
           const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ax), j));
-          y = s + b * y;
+          y = spx_fm_lowpass_step(s, b, y);
           sB[b0 + j] = y;
         }
       }
@@ -90,8 +93,8 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
   // the part of the stream state this stage owns
   struct { float lp, lpf, cur_dur, des_dur; int first_k; } Z;
   if (S.flags & SPX_F_INIT) {
-    Z.lp = 2.14204f;    // speedy.c:263,288
-    Z.lpf = 123.837f;   // speedy.c:264,291
+    Z.lp = SPX_FM_ENERGY_LP0;
+    Z.lpf = SPX_FM_DIFFERENCE_LP0;
     Z.cur_dur = 0.0f; Z.des_dur = 0.0f;
     Z.first_k = -1;
   } else {
@@ -101,7 +104,7 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
   }
   const SpxFrameRec* rec = rec_base + S.frame_off;
   float* scr = scratch_base + (size_t)S.frame_off * 4;  // per frame: comp, hyst, ewld->tension, speed
-  const float lowthr = (float)(0.04 * (double)1.41421f);          // speedy.c:682
+  const float lowthr = SPX_FM_LOW_THRESHOLD;
   float* tfeat = taps.features ? taps.features + (size_t)S.frame_off * SPX_FEATURE_COUNT : nullptr;
 
   // Sequential launches (tile_flags == nullptr): one chunk with every new frame.  Concurrent: chunks of SPX_TCH
@@ -155,8 +158,8 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
         __syncthreads();
         for (int i = tid; i < n; i += NT) {
           const float e = sA[i], l = sB[i];
-          const float local = e / l;                                               // speedy.c:519
-          const float comp = (float)__builtin_sqrt(local > 2 ? 2.0 : (double)local);  // speedy.c:520
+          const float local = spx_fm_local_energy(e, l);
+          const float comp = spx_fm_compress(local);
           const int j = c0 + i;
           scr[4 * j + 0] = comp;
           const int k = j + t0 - F;  // the tension frame whose callback sees these AddData-time values
@@ -174,21 +177,19 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
         float future_max = 0.0f, past_max = 0.0f;
         for (int i = 0; i <= F; i++) {
           const int tau = k + i;  // hysteresis slot `tau` holds frame tau - t0; earlier slots are the zero init
-          float v = (tau >= t0) ? scr[4 * (tau - t0) + 0] : 0.0f;
-          v *= P.taperF[i];
+          const float v = spx_fm_hysteresis_tap((tau >= t0) ? scr[4 * (tau - t0) + 0] : 0.0f, P.taperF[i]);
           if (v > future_max) future_max = v;
         }
         for (int i = 0; i <= Pp; i++) {
           const int tau = k - i;
-          float v = (tau >= t0) ? scr[4 * (tau - t0) + 0] : 0.0f;
-          v *= P.taperP[i];
+          const float v = spx_fm_hysteresis_tap((tau >= t0) ? scr[4 * (tau - t0) + 0] : 0.0f, P.taperP[i]);
           if (v > past_max) past_max = v;
         }
-        const float hyst = (float)((double)(past_max + future_max) / 2.0);  // speedy.c:609
+        const float hyst = spx_fm_hysteresis(past_max, future_max);
         const float e_cur = (k < t0) ? 0.0f : rec[k - t0].energy;          // history slot k holds frame k - t0
-        const bool low = e_cur <= lowthr || k == first_k;                  // the very first call is skipped (speedy.c:692)
+        const bool low = spx_fm_low_energy(e_cur) || k == first_k;   // the very first call is skipped
         const float lsd = low ? 0.0f : rec[k - t0].lsd;
-        const float ewld = low ? 0.0f : lsd * hyst;                          // speedy.c:720
+        const float ewld = low ? 0.0f : spx_fm_weighted(lsd, hyst);
         scr[4 * k + 1] = hyst;
         scr[4 * k + 2] = ewld;
         if (tfeat) {
@@ -211,20 +212,14 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
           const float ewld = sA[i], l = sB[i];
           const float hyst = scr[4 * k + 1];
           const float e_cur = (k < t0) ? 0.0f : rec[k - t0].energy;
-          const bool low = e_cur <= lowthr || k == first_k;
+          const bool low = spx_fm_low_energy(e_cur) || k == first_k;
           float rel = 0.0f, sc = 0.0f;
           if (!low) {
-            rel = (float)((double)ewld / ((double)l + 0.01 * (double)123.979f));       // speedy.c:725-726
-            sc = (float)fmin((double)rel, (double)(4 * 0.971975f));                    // speedy.c:727-728
+            rel = spx_fm_relative(ewld, l);
+            sc = spx_fm_clamp(rel);
           }
-          const float a = 0.5f, b = 0.25f, M_E_ = 0.7f, M_S = 1.0f;
-          const float tension = a * (hyst - M_E_) + b * (sc - M_S);                    // speedy.c:761
-          float v;
-          if ((double)Rg > 1.0) {
-            v = (float)fmax(1.0, (double)(Rg + (1 - Rg) * tension));                   // speedy.c:774
-          } else {
-            v = (float)fmax(0.01, fmin(1.0, (double)(Rg - (1 - Rg) * tension)));       // speedy.c:776
-          }
+          const float tension = spx_fm_tension(hyst, sc);
+          const float v = spx_fm_raw_speed(Rg, tension);
           scr[4 * k + 2] = tension;
           scr[4 * k + 3] = v;
           if (tfeat) {
@@ -239,7 +234,6 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
       Z.lpf = lpf;
       // ---- pass 4: duration feedback (sequential) and blend with the global speed ----
       float cur_dur = Z.cur_dur, des_dur = Z.des_dur;
-      const float fd = (float)(1.0 / 100.0);  // speedy.c:783
       for (int c0 = K0; c0 < ((S.flags & SPX_F_NO_SPEED) ? K0 : K); c0 += SPX_CH) {
         const int n = min(SPX_CH, K - c0);
         for (int i = tid; i < n; i += NT) sA[i] = scr[4 * (c0 + i) + 3];
@@ -248,11 +242,11 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
           // open loop (speedy.c:779 not taken): the requested speeds do not depend on the running sums, so only the
           // two float sums are sequential; quotients and blended speeds are formed 64 at a time
           if (tid < 64) {
-            const float cstep = fd / Rg;
+            const float cstep = spx_fm_frame_time(Rg);
             for (int b0 = 0; b0 < n; b0 += 64) {
               const int m = n - b0 < 64 ? n - b0 : 64;
               const float req = (tid < m) ? sA[b0 + tid] : 1.0f;
-              const float q = fd / req;
+              const float q = spx_fm_frame_time(req);
               if (m == 64) {   // a full block: no per-element bound check
 #pragma unroll
                 for (int j = 0; j < 64; j++) {
@@ -268,20 +262,17 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
                   }
                 }
               }
-              if (tid < m) sB[b0 + tid] = req * nl + Rg * (1 - nl);                      // soniclib.c:344-345
+              if (tid < m) sB[b0 + tid] = spx_fm_blend(req, nl, Rg);
             }
             if (tid == 0) { sA[0] = cur_dur; sA[1] = des_dur; }
           }
         } else if (tid == 0) {
           for (int i = 0; i < n; i++) {
             float req = sA[i];
-            if (fb > 0) {
-              const float excess = cur_dur - des_dur;
-              req = (float)((double)req + fmax(0.01, (double)(fb * excess)));          // speedy.c:780-781
-            }
-            cur_dur += fd / req;
-            des_dur += fd / Rg;
-            sB[i] = req * nl + Rg * (1 - nl);                                          // soniclib.c:344-345
+            if (fb > 0) req = spx_fm_feedback(req, fb, cur_dur, des_dur);
+            cur_dur = spx_fm_advance(cur_dur, req);
+            des_dur = spx_fm_advance(des_dur, Rg);
+            sB[i] = spx_fm_blend(req, nl, Rg);
           }
           sA[0] = cur_dur;  // broadcast the carried sums (sA is re-read only by the next chunk's load)
           sA[1] = des_dur;
@@ -299,14 +290,7 @@ spx_tension_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, SpxSt
       Z.des_dur = des_dur;
     }
     if (speed_ready != nullptr) {
-      // publish: every store of this chunk (speeds, taps) is complete and visible device-wide before the count moves
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(&speed_ready[blockIdx.x], K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      spx_publish_speed_ready(speed_ready, K);   // this chunk's speeds and taps
     } else {
       __syncthreads();
     }
@@ -327,25 +311,14 @@ int spx_tension_vgprs() {
   return spx_kernel_vgprs(reinterpret_cast<const void*>(spx_tension_kernel));
 }
 
-// speedyComputeSpeedFromTension (speedy.c:768-788), one lane, the arithmetic of passes 3 and 4 above for one frame.
+// speedyComputeSpeedFromTension (speedy.c:768-788), one lane: the statements of passes 3 and 4 above for one frame (spx_frame_math.h).
 __global__ void spx_speed_kernel(SpxStreamState* state, float tension, float Rg, float fb, float* speed_out) {
   if (threadIdx.x != 0) return;
-  float v;
-  if ((double)Rg > 1.0) {
-    v = (float)fmax(1.0, (double)(Rg + (1 - Rg) * tension));                   // speedy.c:774
-  } else {
-    v = (float)fmax(0.01, fmin(1.0, (double)(Rg - (1 - Rg) * tension)));       // speedy.c:776
-  }
-  float cur_dur = state->cur_dur, des_dur = state->des_dur;
-  if (fb > 0) {
-    const float excess = cur_dur - des_dur;
-    v = (float)((double)v + fmax(0.01, (double)(fb * excess)));                // speedy.c:780-781
-  }
-  const float fd = (float)(1.0 / 100.0);                                       // speedy.c:783
-  cur_dur += fd / v;
-  des_dur += fd / Rg;
-  state->cur_dur = cur_dur;
-  state->des_dur = des_dur;
+  float v = spx_fm_raw_speed(Rg, tension);
+  const float cur_dur = state->cur_dur, des_dur = state->des_dur;
+  if (fb > 0) v = spx_fm_feedback(v, fb, cur_dur, des_dur);
+  state->cur_dur = spx_fm_advance(cur_dur, v);
+  state->des_dur = spx_fm_advance(des_dur, Rg);
   *speed_out = v;
 }
 void spx_launch_speed_from_tension(SpxStreamState* state, float tension, float Rg, float feedback, float* speed_out,

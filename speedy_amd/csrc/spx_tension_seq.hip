@@ -1,5 +1,6 @@
 // Tension kernel for launches WITHOUT tile flags (kernels in sequence, pipelined and overlapped calls, time chunks, sub-batches):
-// the arithmetic of spx_tension_kernel (spx_tension.hip), operation for operation, in one pass over LDS.
+// the chain of spx_tension_kernel (spx_tension.hip) in one pass over LDS.  Both kernels compile the arithmetic of spx_frame_math.h:
+// they differ in staging, in the waves that run each chain and in polling, not in the text of an operation.
 //
 // spx_tension_kernel makes four passes, each through global memory, and runs its three recurrences one after the other on one
 // lane.  That layout serves the concurrent mode, where the kernel polls tile flags and must stay inside 48 registers and 4 KB of
@@ -20,6 +21,7 @@
 // a large call) loads the compressed energies of the F + Pp frames before its first one, once, with the records of their block.
 // The trip count of the step loop is fixed before it starts: there is no flag, no poll and no sleep in this kernel.
 #include "spx_internal.h"
+#include "spx_frame_math.h"
 
 #define SPX_TSQ_THREADS 256
 #define SPX_TSQ_BLK 64                 // slots per block = lanes of a wave
@@ -31,13 +33,13 @@
 // 64 products a*x[i] in parallel, the chain on lane 0 with a v_readlane per element.  Run by one whole wave; returns the last y.
 __device__ __forceinline__ float tsq_iir_block(const float* x, float* yo, int lo, int hi, float a, float b, float y) {
   const int lane = threadIdx.x & 63;
-  const float ax = a * ((lane >= lo && lane < hi) ? x[lane] : 0.0f);
+  const float ax = spx_fm_lowpass_input(a, (lane >= lo && lane < hi) ? x[lane] : 0.0f);
   if (lo == 0 && hi == SPX_TSQ_BLK) {
     if (lane == 0) {
 #pragma unroll
       for (int j = 0; j < SPX_TSQ_BLK; j++) {
         const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ax), j));
-        y = s + b * y;
+        y = spx_fm_lowpass_step(s, b, y);
         yo[j] = y;
       }
     }
@@ -46,7 +48,7 @@ __device__ __forceinline__ float tsq_iir_block(const float* x, float* yo, int lo
     for (int j = 0; j < SPX_TSQ_BLK; j++) {
       if (j >= lo && j < hi) {  // uniform
         const float s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ax), j));
-        y = s + b * y;
+        y = spx_fm_lowpass_step(s, b, y);
         yo[j] = y;
       }
     }
@@ -65,16 +67,14 @@ __device__ __forceinline__ void tsq_hyst_max(const float* sC, const float* sTF, 
   for (int i = 0; i <= nf; i++) {
     const int tau = k + i;
     const float c = sC[(tau - base) & (SPX_TSQ_RING - 1)];
-    float v = (tau >= t0) ? c : 0.0f;
-    v *= sTF[i];
+    const float v = spx_fm_hysteresis_tap((tau >= t0) ? c : 0.0f, sTF[i]);
     if (v > future_max) future_max = v;
   }
 #pragma unroll
   for (int i = 0; i <= np; i++) {
     const int tau = k - i;
     const float c = sC[(tau - base) & (SPX_TSQ_RING - 1)];
-    float v = (tau >= t0) ? c : 0.0f;
-    v *= sTP[i];
+    const float v = spx_fm_hysteresis_tap((tau >= t0) ? c : 0.0f, sTP[i]);
     if (v > past_max) past_max = v;
   }
 }
@@ -99,8 +99,8 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
   float lp, lpf, cur_dur, des_dur;
   int first_k;
   if (S.flags & SPX_F_INIT) {
-    lp = 2.14204f;    // speedy.c:263,288
-    lpf = 123.837f;   // speedy.c:264,291
+    lp = SPX_FM_ENERGY_LP0;
+    lpf = SPX_FM_DIFFERENCE_LP0;
     cur_dur = 0.0f; des_dur = 0.0f;
     first_k = -1;
   } else {
@@ -110,7 +110,7 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
   }
   const SpxFrameRec* rec = rec_base + S.frame_off;
   float* scr = scratch_base + (size_t)S.frame_off * 4;  // per frame: comp, hyst, tension, speed
-  const float lowthr = (float)(0.04 * (double)1.41421f);          // speedy.c:682
+  const float lowthr = SPX_FM_LOW_THRESHOLD;
   float* tfeat = taps.features ? taps.features + (size_t)S.frame_off * SPX_FEATURE_COUNT : nullptr;
 
   // the tension frames of this job, as spx_tension.hip forms them
@@ -151,7 +151,6 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
   if (wave == 0 && nb > 0) prefetch(0);
   __syncthreads();
 
-  const float fd = (float)(1.0 / 100.0);  // speedy.c:783
   const int steps = nb > 0 ? nb + SPX_TSQ_NBLK : 0;
   for (int s = 0; s < steps; s++) {
     if (wave == 0) {
@@ -182,11 +181,11 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
           if (F == 12 && Pp == 8) tsq_hyst_max<12, 8>(sC, sTF, sTP, k, base, t0, F, Pp, future_max, past_max);
           else if (F == 8 && Pp == 12) tsq_hyst_max<8, 12>(sC, sTF, sTP, k, base, t0, F, Pp, future_max, past_max);
           else tsq_hyst_max<0, 0>(sC, sTF, sTP, k, base, t0, F, Pp, future_max, past_max);
-          const float hyst = (float)((double)(past_max + future_max) / 2.0);  // speedy.c:609
+          const float hyst = spx_fm_hysteresis(past_max, future_max);
           const float e_cur = (k < t0) ? 0.0f : sE[r];                        // slot k holds frame k - t0
-          const bool low = e_cur <= lowthr || k == first_k;                   // the very first call is skipped (speedy.c:692)
+          const bool low = spx_fm_low_energy(e_cur) || k == first_k;          // the very first call is skipped
           const float lsd = low ? 0.0f : sL[r];
-          const float ewld = low ? 0.0f : lsd * hyst;                          // speedy.c:720
+          const float ewld = low ? 0.0f : spx_fm_weighted(lsd, hyst);
           sH[r] = hyst;
           sW[r] = ewld;
           if (tfeat) {
@@ -205,20 +204,14 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
           const float ewld = sW[r], l = sLF[r];
           const float hyst = sH[r];
           const float e_cur = (k < t0) ? 0.0f : sE[r];
-          const bool low = e_cur <= lowthr || k == first_k;
+          const bool low = spx_fm_low_energy(e_cur) || k == first_k;
           float rel = 0.0f, sc = 0.0f;
           if (!low) {
-            rel = (float)((double)ewld / ((double)l + 0.01 * (double)123.979f));       // speedy.c:725-726
-            sc = (float)fmin((double)rel, (double)(4 * 0.971975f));                    // speedy.c:727-728
+            rel = spx_fm_relative(ewld, l);
+            sc = spx_fm_clamp(rel);
           }
-          const float a = 0.5f, bq = 0.25f, M_E_ = 0.7f, M_S = 1.0f;
-          const float tension = a * (hyst - M_E_) + bq * (sc - M_S);                   // speedy.c:761
-          float v;
-          if ((double)Rg > 1.0) {
-            v = (float)fmax(1.0, (double)(Rg + (1 - Rg) * tension));                   // speedy.c:774
-          } else {
-            v = (float)fmax(0.01, fmin(1.0, (double)(Rg - (1 - Rg) * tension)));       // speedy.c:776
-          }
+          const float tension = spx_fm_tension(hyst, sc);
+          const float v = spx_fm_raw_speed(Rg, tension);
           sV[r] = v;
           scr[4 * k + 1] = hyst;
           scr[4 * k + 2] = tension;
@@ -240,10 +233,10 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
         if (h3 > l3) {
           if (!(fb > 0)) {
             // open loop (speedy.c:779 not taken): only the two float sums are sequential
-            const float cstep = fd / Rg;
+            const float cstep = spx_fm_frame_time(Rg);
             const bool mine = lane >= l3 && lane < h3;
             const float req = mine ? sV[r0 + lane] : 1.0f;
-            const float q = fd / req;
+            const float q = spx_fm_frame_time(req);
             if (lane == 0) {
               if (l3 == 0 && h3 == BLK) {
 #pragma unroll
@@ -261,17 +254,14 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
                 }
               }
             }
-            if (mine) sS[r0 + lane] = req * nl + Rg * (1 - nl);                          // soniclib.c:344-345
+            if (mine) sS[r0 + lane] = spx_fm_blend(req, nl, Rg);
           } else if (lane == 0) {
             for (int i = l3; i < h3; i++) {
               float req = sV[r0 + i];
-              if (fb > 0) {
-                const float excess = cur_dur - des_dur;
-                req = (float)((double)req + fmax(0.01, (double)(fb * excess)));          // speedy.c:780-781
-              }
-              cur_dur += fd / req;
-              des_dur += fd / Rg;
-              sS[r0 + i] = req * nl + Rg * (1 - nl);                                     // soniclib.c:344-345
+              if (fb > 0) req = spx_fm_feedback(req, fb, cur_dur, des_dur);
+              cur_dur = spx_fm_advance(cur_dur, req);
+              des_dur = spx_fm_advance(des_dur, Rg);
+              sS[r0 + i] = spx_fm_blend(req, nl, Rg);
             }
           }
           cur_dur = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, cur_dur)));
@@ -285,8 +275,8 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
         const int j = base + b * BLK + lane - t0;
         if (j >= fa && j < T) {
           const float e = sE[r], l = sLP[r];
-          const float local = e / l;                                               // speedy.c:519
-          const float comp = (float)__builtin_sqrt(local > 2 ? 2.0 : (double)local);  // speedy.c:520
+          const float local = spx_fm_local_energy(e, l);
+          const float comp = spx_fm_compress(local);
           sC[r] = comp;
           scr[4 * j + 0] = comp;
           const int k = j + t0 - F;  // the tension frame whose callback sees these AddData-time values
@@ -327,16 +317,7 @@ spx_tension_seq_kernel(SpxPlanDev P, const SpxStreamDev* __restrict__ streams, S
     else if (wave == 1) o.lpf = lpf;
     else if (wave == 2) { o.cur_dur = cur_dur; o.des_dur = des_dur; }
   }
-  if (speed_ready != nullptr) {
-    // publish: every store of this job (speeds, taps, state) is complete and visible device-wide before the count moves
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&speed_ready[blockIdx.x], K, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if (speed_ready != nullptr) spx_publish_speed_ready(speed_ready, K);   // this job's speeds, taps and state
 }
 
 void spx_launch_tension_seq(const SpxPlanDev& P, const SpxStreamDev* streams, int n_streams, SpxStreamState* states,
