@@ -86,6 +86,11 @@ size_t spx_batch_workspace_bytes(spx_plan_t plan, const spx_stream_job* jobs, in
  *   out  DEVICE  int16 output samples (written once)
  *   n_out DEVICE int64[n_streams]: produced frames per stream (negative = out_cap overflow)
  * Returns 0 when the launches were enqueued.
+ * What the workspace, out, n_out and the taps hold when the call is made does not matter, nor what lies in `in` between the jobs'
+ * streams and in the 64 values behind the last one: every state the kernels keep starts from the call's own staging (memory fresh
+ * from hipMalloc, a workspace another table's call has used).  in, out and the taps need the alignment of their element type only;
+ * nothing is written outside out_off .. out_off + out_cap * channels of a job and the job's rows of the taps.  That holds for every
+ * batch call below (tests/test_gpu_dirty_memory.py).
  * The reference stores any float as speed, nonlinear factor or feedback strength and has no defined behaviour for most of them.
  * Here a job is taken if channels >= 1, no count or offset is negative, the speed is finite and > 0, the nonlinear factor lies in
  * [0, 1], the feedback strength is finite, n_in < 2^30 and -- a nonlinear job -- the plan's analysis tile fits one CU's LDS;
@@ -106,7 +111,8 @@ int spx_batch_run(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, co
  * the bytes and the count spx_batch_run gives it, in the same call as jobs with other rates.  Taps are spx_batch_run's (the rate
  * stage lies behind everything they observe); spx_batch_pack_outputs and spx_batch_read_steps work on the result unchanged.
  * A rate <= 0, not finite, or so large that (int)(sample rate / rate) < 1 is refused: -1, spx_last_error, nothing launched.
- * The workspace (spx_batch_workspace_bytes_rate) also holds the speed stage's output of the jobs with a rate other than 1.
+ * The workspace (spx_batch_workspace_bytes_rate) also holds the speed stage's output of the jobs with a rate other than 1; its
+ * contents on entry do not matter.
  * Asynchronous on hip_stream like spx_batch_run, kernels in sequence; the plain call only (no _ahead / _overlapped / _mixed form).
  * The pipeline object takes a rate per lane and per batch: spx_pipeline_create_rate below.  Any channel count the walk kernel's window takes: the 16 of the streaming API's rate
  * stage do not apply. */
@@ -133,7 +139,8 @@ int64_t spx_plan_out_capacity_rate(spx_plan_t plan, int64_t n_in, float speed, f
  * the lag is that input at the speed of the moment: up to 221 frames at 3.5x, 428 at 1.2x and 1 579 at 0.5x on the directed 16 kHz
  * jobs (profiles/edit_lookup.txt).  (The integral of 1 / speed over the speed tap is no substitute: it drifts from these rows.)
  *   map  DEVICE int64; stream i's rows start at the sum of spx_plan_map_rows of the streams in front of it, in job order.
- * out, n_out and the taps are byte for byte spx_batch_run's for the same table; the workspace is spx_batch_workspace_bytes.  The
+ * out, n_out and the taps are byte for byte spx_batch_run's for the same table; the workspace is spx_batch_workspace_bytes (its contents
+ * on entry, like those of out, n_out, the taps and `map`, do not matter).  The
  * call refuses what spx_batch_run refuses, with the same messages, and a NULL map -- -1, spx_last_error, nothing enqueued.  The rows
  * of a job whose n_out comes back negative are unspecified.
  * COST: the whole batch runs on the GENERAL walk kernel (the speed-up kernels write no map yet), kernels in sequence on hip_stream,
@@ -216,7 +223,8 @@ int spx_batch_run_float_map(spx_plan_t plan, const spx_stream_job* jobs, const f
  *   n_ops    DEVICE int64[n_streams]: the number of records of each job.  A job that has more than ops_cap[i] comes back as MINUS the
  *            number it has: the kernel keeps counting and stops storing, nothing is written behind the stream's region, out and
  *            n_out are unaffected -- call again with that capacity.  Where n_out[i] is negative the stream's records are unspecified.
- * out, n_out and the taps are byte for byte spx_batch_run's for the same table; the workspace is spx_batch_workspace_bytes.  Refused
+ * out, n_out and the taps are byte for byte spx_batch_run's for the same table; the workspace is spx_batch_workspace_bytes (its contents
+ * on entry, like those of out, n_out, the taps, ops and n_ops, do not matter).  Refused
  * with -1 and spx_last_error, nothing enqueued, the plan as it was: everything spx_batch_run refuses, with its messages; a NULL or
  * misaligned ops, a NULL ops_cap or n_ops; a negative capacity; more than 2^31 - 1 records of capacity in one call.
  * COST: as spx_batch_run_map -- the whole batch on the GENERAL walk kernel, kernels in sequence on hip_stream -- plus one 16-byte
@@ -384,7 +392,9 @@ int spx_edit_replay_scaled(spx_plan_t plan, const spx_stream_job* jobs, int n_st
  *   a, b      DEVICE float rows;  results  DEVICE [n_pairs];  path  DEVICE: n_a + n_b - 1 entries per pair from path_off -- the
  *             regions are the caller's, not checked for overlap; entries at or behind n_path are not written
  *   workspace DEVICE, spx_dtw_workspace_bytes (0 with spx_last_error for a table the call refuses): two bits per cell of direction,
- *             rounded up to 64 columns, and 16 bytes per row and column -- the cost matrix itself is never stored
+ *             rounded up to 64 columns, and 16 bytes per row and column -- the cost matrix itself is never stored.  Its contents
+ *             on entry do not matter (a partial tile writes its own cells' bits and zeros in the rest of its words), nor do
+ *             those of results and path
  *   plan      the device, and the staging of the job table: what spx_edit_replay and spx_map_lookup use it for.  The sample rate
  *             plays no part.
  * Asynchronous on hip_stream; nothing comes back to the host.  Refused with -1 and spx_last_error, nothing enqueued, the outputs
@@ -423,7 +433,8 @@ int spx_batch_dtw(spx_plan_t plan, const spx_dtw_job* jobs, int n_pairs, int dim
  * the final table; a NULL n_probe or speeds; a seconds[i] that is negative or not finite; a want whose float value is not finite and
  * > 0 (LENGTH on an empty stream is one); a stream with want * want * (out_cap + 1) >= 1e18 -- the bound that keeps every speed the
  * device can compute inside the range the walk kernels serve; a workspace smaller than spx_batch_workspace_bytes_twopass (the probe
- * table's spx_batch_workspace_bytes and the retarget table behind it; 0 with spx_last_error for a table that is refused).
+ * table's spx_batch_workspace_bytes and the retarget table behind it; 0 with spx_last_error for a table that is refused;
+ * what it, out, n_out, n_probe, speeds and the taps hold on entry does not matter).
  * CAPACITY: spx_plan_out_capacity_twopass(n_in, want, nonlinear) is the larger of spx_plan_out_capacity_for(n_in, (float)want, 1)
  * -- the probe -- and spx_plan_out_capacity_for(n_in, (float)want, nonlinear); -1 for values spx_batch_run refuses.  What that covers
  * of the final pass, whose speed is not known beforehand:
@@ -472,6 +483,7 @@ int spx_debug_last_twopass(void);
  * bit for bit) on int16 stagings inside the workspace, then the output conversion, which reads n_out on the device.  Taps are
  * passed through.  The workspace (spx_batch_workspace_bytes_float, 256-byte aligned as every device allocation is) begins with the
  * int16 call's own workspace, so spx_batch_read_steps works on it; behind it lie the table and the two stagings.
+ * Its contents on entry do not matter, nor those of out, n_out and the taps.
  * Refused with -1 and spx_last_error, nothing launched: everything the int16 call refuses (a bad speed, rate, nonlinear factor ...),
  * a null pointer, in or out not 4-byte aligned, a workspace that is too small.
  * NOT offered on float samples: the _ahead / _overlapped / _mixed* forms on caller-owned buffers and spx_batch_pack_outputs.  (The
@@ -839,6 +851,12 @@ int spx_debug_log_check(unsigned first_block, unsigned end_block, unsigned long 
  * pipelined with the previous call (spx_batch_run_ahead), 0 if it launched its kernels in sequence (another process holds the
  * device's concurrent-mode lock, spx_set_concurrent(0), the batch shape). */
 int spx_debug_last_call_concurrent(void);
+/* Diagnostics: what the library's own long-lived device allocations hold when they are new -- pipeline slots, the pool's workspace,
+ * block cache and record arrays, the state of the drop-in stream API and of the unit-level API.  byte = 0 .. 255: every such block
+ * allocated from now on is filled with that byte before anything else uses it (in place of the clearing some of them get);
+ * -1 (the default, and any other value): off, the library makes exactly the calls it makes without the switch.  Read when a block is
+ * allocated, never on a launch path.  Results must not depend on it (tests/test_gpu_dirty_owned.py). */
+void spx_debug_set_alloc_fill(int byte);
 /* Sum over the same calls of the frame-rate (tension) kernel's time, as of the last spx_timing_collect. */
 double spx_timing_last_tension_ms(void);
 /* ... and of the rate kernel's (spx_batch_run_rate calls with a rate other than 1). */

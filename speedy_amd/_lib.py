@@ -135,6 +135,7 @@ SYMBOLS = {
     "spx_debug_last_walk_form": (C.c_int, []),
     "spx_debug_kernel_vgprs": (C.c_int, [C.c_int]),
     "spx_debug_last_call_concurrent": (C.c_int, []),
+    "spx_debug_set_alloc_fill": (None, [C.c_int]),
     "spx_debug_fdiv_check": (C.c_longlong, [C.c_uint, C.c_uint, C.c_int, C.c_int]),
     "spx_debug_xfade_check": (C.c_longlong, [C.c_int, C.c_int]),
     "spx_debug_select_check": (C.c_int, [C.POINTER(C.c_uint), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint)]),

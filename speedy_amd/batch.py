@@ -895,8 +895,9 @@ class Pipeline:
             assert x.dtype == self._torch_dt and x.is_contiguous() and x.numel() >= extent
             # (include/speedy_hip.h: an int16 device input is used in place and must be allocated 64 values past the last stream's end;
             # a float one is read by the conversion, exactly over the jobs' values)
-            assert self.float_samples or not x.is_cuda or x.numel() >= self.total_in + 64, \
-                "device input: allocate spx_pipeline_input_values() + 64 int16 values"
+            if not self.float_samples and x.is_cuda and x.numel() < self.total_in + 64:
+                raise ValueError("device input: allocate spx_pipeline_input_values() + 64 int16 values (%d), not %d"
+                                 % (self.total_in + 64, x.numel()))
             return x, x.data_ptr(), x.is_cuda
         x = np.ascontiguousarray(x, self._np_dt)
         assert x.size >= extent

@@ -113,7 +113,7 @@ sonicStream speedyHipCreateSonicStreamEx(int sampleRate, int numChannels, int ma
   const size_t small = 256 + sizeof(SpxStreamState) + sizeof(int64_t) + sizeof(SpxRateState) + 64;
   if (hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&s->evStaged, hipEventDisableTiming) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->dSmall), small) != hipSuccess) {
+      spx_dev_alloc(&s->dSmall, small) != hipSuccess) {
     g_api_err = "sonicCreateStream: device allocation failed";
     sonicDestroyStream(s);
     return nullptr;

@@ -190,7 +190,7 @@ void* spx_pool_block_alloc(SpxPool* P, size_t bytes, size_t* got) {
   *got = (size_t)1 << l;
   if (!P->blocks[l].empty()) { void* q = P->blocks[l].back(); P->blocks[l].pop_back(); return q; }
   void* q = nullptr;
-  if (hipMalloc(&q, *got) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  if (spx_dev_alloc(&q, *got) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
   return q;
 }
 static void block_free_locked(SpxPool* P, void* p, size_t bytes) {
@@ -209,8 +209,8 @@ static bool arena_grow(SpxPool* P, int64_t min_cap) {
   while (ncap < min_cap) ncap *= 2;
   SpxFrameRec* nr = nullptr;
   float* ns = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&nr), sizeof(SpxFrameRec) * (size_t)ncap) != hipSuccess) return false;
-  if (hipMalloc(reinterpret_cast<void**>(&ns), sizeof(float) * 4 * (size_t)ncap) != hipSuccess) { (void)hipFree(nr); return false; }
+  if (spx_dev_alloc(&nr, sizeof(SpxFrameRec) * (size_t)ncap) != hipSuccess) return false;
+  if (spx_dev_alloc(&ns, sizeof(float) * 4 * (size_t)ncap) != hipSuccess) { (void)hipFree(nr); return false; }
   if (P->aRec) {   // everything moves; the handles' pointers follow (offsets relative to the arena base do not change)
     (void)hipMemcpyAsync(nr, P->aRec, sizeof(SpxFrameRec) * (size_t)P->aBump, hipMemcpyDeviceToDevice, P->hs);
     (void)hipMemcpyAsync(ns, P->aScr, sizeof(float) * 4 * (size_t)P->aBump, hipMemcpyDeviceToDevice, P->hs);
@@ -532,7 +532,7 @@ static RunLaunch launch_run(SpxPool* P, std::unique_lock<std::mutex>& lk) {
     P->dWs = nullptr;
     size_t cap = P->dWsCap ? P->dWsCap : 65536;
     while (cap < w_total) cap *= 2;
-    if (hipMalloc(reinterpret_cast<void**>(&P->dWs), cap) != hipSuccess) { P->dWs = nullptr; P->dWsCap = 0; (void)hipGetLastError(); return give_up("pool workspace allocation failed"); }
+    if (spx_dev_alloc(&P->dWs, cap) != hipSuccess) { P->dWs = nullptr; P->dWsCap = 0; (void)hipGetLastError(); return give_up("pool workspace allocation failed"); }
     P->dWsCap = cap;
   }
   SpxStreamDev* hA = reinterpret_cast<SpxStreamDev*>(P->hTab.p);
@@ -866,8 +866,8 @@ bool spx_pool_leave(sonicStream s) {
     SpxFrameRec* nr = nullptr;
     float* ns = nullptr;
     const int64_t cap = s->arenaCap;
-    if (hipMallocAsync(reinterpret_cast<void**>(&nr), sizeof(SpxFrameRec) * (size_t)cap, P->hs) != hipSuccess ||
-        hipMallocAsync(reinterpret_cast<void**>(&ns), sizeof(float) * 4 * (size_t)cap, P->hs) != hipSuccess ||
+    if (spx_dev_alloc_on(&nr, sizeof(SpxFrameRec) * (size_t)cap, P->hs) != hipSuccess ||
+        spx_dev_alloc_on(&ns, sizeof(float) * 4 * (size_t)cap, P->hs) != hipSuccess ||
         hipMemcpyAsync(nr, s->dRec.p, sizeof(SpxFrameRec) * (size_t)cap, hipMemcpyDeviceToDevice, P->hs) != hipSuccess ||
         hipMemcpyAsync(ns, s->dScr.p, sizeof(float) * 4 * (size_t)cap, hipMemcpyDeviceToDevice, P->hs) != hipSuccess ||
         hipStreamSynchronize(P->hs) != hipSuccess) {

@@ -64,7 +64,7 @@ struct SlideBuf {
       if (!np) return false;
       ncap = (int64_t)((nblock - 16) / sizeof(T)) - guard;   // the whole block is usable
       ncap -= ncap % A;
-    } else if (hipMallocAsync(reinterpret_cast<void**>(&np), (size_t)(ncap + guard) * sizeof(T) + 16, st) != hipSuccess) {
+    } else if (spx_dev_alloc_on(&np, (size_t)(ncap + guard) * sizeof(T) + 16, st) != hipSuccess) {
       return false;
     }
     if (guard) {

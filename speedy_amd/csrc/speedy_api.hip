@@ -75,7 +75,8 @@ static bool grow(speedyStream s, int64_t need_hi) {
                  {reinterpret_cast<void**>(&s->tSpec), sizeof(float), P.N, nullptr},
                  {reinterpret_cast<void**>(&s->tNorm), sizeof(float), P.W, nullptr}};
   for (Arr& a : arrs) {
-    if (hipMallocAsync(&a.np, (size_t)ncap * a.stride * a.elem, s->hs) != hipSuccess) {
+    // (cleared as always; under spx_debug_set_alloc_fill filled with its byte instead: spx_dev_alloc_on)
+    if (spx_dev_alloc_on(&a.np, (size_t)ncap * a.stride * a.elem, s->hs, true) != hipSuccess) {
       (void)hipGetLastError();
       for (Arr& b : arrs) if (b.np) (void)hipFreeAsync(b.np, s->hs);
       return false;   // nothing has moved: the stream is as it was
@@ -85,7 +86,6 @@ static bool grow(speedyStream s, int64_t need_hi) {
     unsigned char* np = static_cast<unsigned char*>(a.np);
     unsigned char* op = static_cast<unsigned char*>(*a.p);
     const size_t row = (size_t)a.stride * a.elem;
-    (void)hipMemsetAsync(np, 0, (size_t)ncap * row, s->hs);
     if (op && keep_hi > keep_lo) {
       const int64_t n = std::min(keep_hi, s->origin + s->cap) - keep_lo;
       if (n > 0)
@@ -284,10 +284,10 @@ speedyStream speedyCreateStream(int sample_rate) {
   (void)hipGetDevice(&s->device);
   const SpxPlanDev& P = *plan;
   if (hipStreamCreateWithFlags(&s->hs, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->dSmall), 1024) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->dScratchFrame), sizeof(float) * 2 * P.W) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->dScratchSpec), sizeof(float) * 2 * P.N) != hipSuccess ||
-      hipMalloc(reinterpret_cast<void**>(&s->dHook), sizeof(float) * (64 + 6 * (size_t)P.N)) != hipSuccess) {
+      spx_dev_alloc(&s->dSmall, 1024) != hipSuccess ||
+      spx_dev_alloc(&s->dScratchFrame, sizeof(float) * 2 * P.W) != hipSuccess ||
+      spx_dev_alloc(&s->dScratchSpec, sizeof(float) * 2 * P.N) != hipSuccess ||
+      spx_dev_alloc(&s->dHook, sizeof(float) * (64 + 6 * (size_t)P.N)) != hipSuccess) {
     spx_internal_set_api_error("speedyCreateStream: device allocation failed");
     speedyDestroyStream(s);
     return nullptr;
@@ -517,7 +517,7 @@ static void hook_ensure_state(speedyStream s) {
 FirstOrderFilter CreateFirstOrderFilter(float time_constant_in_samples) {          // speedy.c:50-60
   FirstOrderFilter f = new FirstOrderFilterStruct();
   (void)hipGetDevice(&f->device);
-  if (hipMalloc(reinterpret_cast<void**>(&f->d), 4 * sizeof(float)) != hipSuccess) { delete f; return nullptr; }
+  if (spx_dev_alloc(&f->d, 4 * sizeof(float)) != hipSuccess) { delete f; return nullptr; }
   DesignFirstOrderLowpassFilter(f, time_constant_in_samples);
   return f;
 }

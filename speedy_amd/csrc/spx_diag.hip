@@ -2,6 +2,8 @@
 // the process-wide switches, timing collection, output packing, copies.
 #include "spx_engine.h"
 
+int g_spx_alloc_fill = -1;   // spx_debug_set_alloc_fill (spx_internal.h: spx_dev_alloc)
+
 extern "C" {
 // Names of the kernels a batch of this shape is served by, as a profiler prints them (without "void" and the argument
 // list): "analysis;tension;walk".  bench.py keys its roofline object and profiles/pmc_traffic.json with them.
@@ -119,6 +121,7 @@ void* spx_device_alloc(size_t bytes) {
   return p;
 }
 void spx_device_free(void* p) { if (p) (void)hipFree(p); }
+void spx_debug_set_alloc_fill(int byte) { __atomic_store_n(&g_spx_alloc_fill, (byte >= 0 && byte <= 255) ? byte : -1, __ATOMIC_RELAXED); }
 int spx_copy_to_device(void* dst, const void* src, size_t bytes, void* hs) {
   HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, static_cast<hipStream_t>(hs)));
   return 0;

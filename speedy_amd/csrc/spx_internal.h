@@ -326,6 +326,37 @@ int spx_analysis_small_tile_frames();
 int spx_analysis_tiny_tile_frames();
 int spx_analysis_prefers_small_tile(const SpxPlanDev& P);
 
+// The library's long-lived device allocations (pipeline slots, the pool's workspace and record arrays, the stream and unit APIs'
+// state) go through this one helper.  g_spx_alloc_fill (spx_debug_set_alloc_fill, spx_diag.hip): -1 (default) = hipMalloc /
+// hipMallocAsync and, where the site always cleared its block (zero), the fill with 0 it made before -- nothing else; 0 .. 255 = the
+// new block is filled with that byte before anything else uses it, INSTEAD of the clearing, so that a kernel that relies on fresh
+// memory being zero shows (tests/test_gpu_dirty_owned.py).  Read at allocation time only.
+// spx_dev_alloc: hipMalloc, the fill on the null stream.  spx_dev_alloc_on: the fill on `st`, the stream whose work uses the block
+// first; from_pool: hipMallocAsync on `st` instead of hipMalloc.
+extern int g_spx_alloc_fill;
+template <typename T>
+static inline hipError_t spx_dev_alloc_impl(T** p, size_t bytes, bool zero, bool on_stream, bool from_pool, hipStream_t st) {
+  void* q = nullptr;
+  const hipError_t e = from_pool ? hipMallocAsync(&q, bytes, st) : hipMalloc(&q, bytes);
+  if (e != hipSuccess) return e;
+  *p = static_cast<T*>(q);
+  const int fill = __atomic_load_n(&g_spx_alloc_fill, __ATOMIC_RELAXED);
+  if (fill < 0 && !zero) return hipSuccess;
+  const int v = fill < 0 ? 0 : (fill & 255);
+  if (on_stream) return hipMemsetAsync(q, v, bytes, st);
+  const hipError_t m = hipMemset(q, v, bytes);
+  // (a debug fill on the null stream: the library's own streams do not wait for that stream, so the host does)
+  return (m == hipSuccess && fill >= 0) ? hipStreamSynchronize(nullptr) : m;
+}
+template <typename T>
+static inline hipError_t spx_dev_alloc(T** p, size_t bytes, bool zero = false) {
+  return spx_dev_alloc_impl(p, bytes, zero, false, false, nullptr);
+}
+template <typename T>
+static inline hipError_t spx_dev_alloc_on(T** p, size_t bytes, hipStream_t st, bool zero = false, bool from_pool = true) {
+  return spx_dev_alloc_impl(p, bytes, zero, true, from_pool, st);
+}
+
 // Shared, cached plan per (sample rate, hysteresis mode); owned by the library for the process lifetime.
 struct spx_plan;
 int64_t spx_internal_out_bound(const SpxPlanDev& P, int64_t n_in, float speed, bool nonlinear);

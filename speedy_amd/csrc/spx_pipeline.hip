@@ -285,7 +285,7 @@ static int pipeline_build(spx_pipeline* p) {
   PCHK(hipStreamCreateWithFlags(&p->s_run, hipStreamNonBlocking));
   PCHK(hipStreamCreateWithFlags(&p->s_h2d, hipStreamNonBlocking));
   const size_t tab_bytes = (size_t)n * (2 * sizeof(int64_t) + sizeof(int));
-  PCHK(hipMalloc(reinterpret_cast<void**>(&p->d_tab), tab_bytes));
+  PCHK(spx_dev_alloc(&p->d_tab, tab_bytes));
   PCHK(hipMemcpy(p->d_tab, tab.data(), (size_t)n * 2 * sizeof(int64_t), hipMemcpyHostToDevice));
   PCHK(hipMemcpy(reinterpret_cast<unsigned char*>(p->d_tab) + (size_t)n * 2 * sizeof(int64_t), chans.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
   p->slots.resize((size_t)p->depth);
@@ -293,13 +293,11 @@ static int pipeline_build(spx_pipeline* p) {
   const bool flt = (p->flags & SPX_PIPELINE_FLOAT) != 0;
   for (auto& S : p->slots) {
     // (d_in: allocated by the first submit of host memory -- a caller whose input is device-resident never needs it)
-    PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_out), (p->out_values + 64) * sizeof(int16_t)));
-    PCHK(hipMemset(S.d_out, 0, (p->out_values + 64) * sizeof(int16_t)));
-    PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_nout), (size_t)n * sizeof(int64_t)));
-    PCHK(hipMemset(S.d_nout, 0, (size_t)n * sizeof(int64_t)));
-    PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_offsets), ((size_t)n + 1) * sizeof(int64_t)));
-    PCHK(hipMalloc(&S.ws, p->ws_bytes));
-    PCHK(hipMemset(S.ws, 0, p->ws_bytes));
+    // (cleared once as always; under spx_debug_set_alloc_fill filled with its byte instead: spx_dev_alloc)
+    PCHK(spx_dev_alloc(&S.d_out, (p->out_values + 64) * sizeof(int16_t), true));
+    PCHK(spx_dev_alloc(&S.d_nout, (size_t)n * sizeof(int64_t), true));
+    PCHK(spx_dev_alloc(&S.d_offsets, ((size_t)n + 1) * sizeof(int64_t)));
+    PCHK(spx_dev_alloc(&S.ws, p->ws_bytes, true));
     if (host_out) {
       if (flt) PCHK(hipHostMalloc(reinterpret_cast<void**>(&S.h_outf), (p->out_values + 64) * sizeof(float), hipHostMallocDefault));
       else PCHK(hipHostMalloc(reinterpret_cast<void**>(&S.h_out), (p->out_values + 64) * sizeof(int16_t), hipHostMallocDefault));
@@ -307,13 +305,11 @@ static int pipeline_build(spx_pipeline* p) {
     }
     if (flt) {
       // the int16 staging the engine reads, + 64 values as always, zeroed once (the conversion writes the jobs' values only)
-      PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_in), (p->in_values + 64) * sizeof(int16_t)));
-      PCHK(hipMemset(S.d_in, 0, (p->in_values + 64) * sizeof(int16_t)));
+      PCHK(spx_dev_alloc(&S.d_in, (p->in_values + 64) * sizeof(int16_t), true));
       PCHK(hipHostMalloc(&S.h_cv, spx_conv_table_bytes(n), hipHostMallocDefault));
-      PCHK(hipMalloc(&S.d_cv, spx_conv_table_bytes(n)));
+      PCHK(spx_dev_alloc(&S.d_cv, spx_conv_table_bytes(n)));
       if (!host_out) {
-        PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_outf), (p->out_values + 64) * sizeof(float)));
-        PCHK(hipMemset(S.d_outf, 0, (p->out_values + 64) * sizeof(float)));
+        PCHK(spx_dev_alloc(&S.d_outf, (p->out_values + 64) * sizeof(float), true));
       }
     }
     PCHK(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
@@ -414,7 +410,7 @@ static int pipeline_float_input(spx_pipeline_t p, SpxPipeSlot& S, size_t extent,
   if (spx_conv_table_fill(S.h_cv, S.jobs.data(), p->n, &max_in, max_out)) return pfail(-1, "spx_pipeline: a lane too large for one conversion launch");
   const float* src = in;
   if (!in_is_device) {
-    if (!S.d_inf) PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_inf), (p->in_values + 16) * sizeof(float)));   // (+ 16: never empty)
+    if (!S.d_inf) PCHK(spx_dev_alloc_on(&S.d_inf, (p->in_values + 16) * sizeof(float), p->s_h2d, false, false));   // (+ 16: never empty)
     if (extent) PCHK(hipMemcpyAsync(S.d_inf, in, extent * sizeof(float), hipMemcpyHostToDevice, p->s_h2d));
     src = S.d_inf;
   }
@@ -457,8 +453,7 @@ static int64_t pipeline_submit(spx_pipeline_t p, const spx_stream_job* jobs, con
     if (!S.d_in) {
       // + 64 values behind the input: the walk kernels' aligned window refill may read a few frames past a stream's end; zeroed
       // once, never written again
-      PCHK(hipMalloc(reinterpret_cast<void**>(&S.d_in), (p->in_values + 64) * sizeof(int16_t)));
-      PCHK(hipMemsetAsync(S.d_in, 0, (p->in_values + 64) * sizeof(int16_t), p->s_h2d));
+      PCHK(spx_dev_alloc_on(&S.d_in, (p->in_values + 64) * sizeof(int16_t), p->s_h2d, true, false));
     }
     // (this batch's extent only: what lies behind it in d_in -- an earlier batch's samples -- is padding no lane of this batch reads)
     if (extent) PCHK(hipMemcpyAsync(S.d_in, in, extent * sizeof(int16_t), hipMemcpyHostToDevice, p->s_h2d));

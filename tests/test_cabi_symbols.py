@@ -40,6 +40,16 @@ def test_python_binding_covers_the_headers():
     assert declared <= set(SYMBOLS), sorted(declared - set(SYMBOLS))
 
 
+def test_the_debug_switches_the_dirty_memory_tests_use_are_declared_and_bound():
+    """tests/test_gpu_dirty_memory.py and tests/test_gpu_dirty_owned.py reach every launch form and the allocation fill through these."""
+    from speedy_amd._lib import SYMBOLS
+    need = ["spx_debug_set_alloc_fill", "spx_set_concurrent", "spx_set_tension_form", "spx_set_pipeline_chunks", "spx_debug_last_walk_form",
+            "spx_debug_last_call_concurrent", "spx_debug_last_tension_form", "spx_debug_last_call_chunks"]
+    declared = set(declared_functions("speedy_hip.h"))
+    assert set(need) <= declared and set(need) <= set(SYMBOLS), sorted(set(need) - (declared & set(SYMBOLS)))
+    assert SYMBOLS["spx_debug_set_alloc_fill"] == (None, [ctypes.c_int])
+
+
 def test_reference_api_surface_present():
     """Every function of the reference's public header (sonic2.h:54-125) exists with the same name."""
     ref = ["sonicCreateStream", "sonicDestroyStream", "sonicWriteShortToStream", "sonicReadShortFromStream",
