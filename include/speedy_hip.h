@@ -345,9 +345,9 @@ int spx_edit_lookup(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, 
  * y_out not aligned to the sample size; a stream with S(min(jobs[i].out_cap, 2^31 - 1)) or S(L) above 2^31 - 1 (master positions
  * fit int32 inside the kernel, as the key's do in spx_edit_replay's).
  * COST: one pass over the master's bytes, spx_edit_replay's kernel shape with the records scaled once per block.
- * OUT OF SCOPE: p < q (label or feature tracks below the key's rate: they need record compaction); resampling the master down to
- * the key, which stays the caller's job; lookups in master frames (scale the queries of spx_edit_lookup with spx_edit_scale); the
- * pipeline object. */
+ * OUT OF SCOPE: resampling the master down to the key, which stays the caller's job; lookups in master frames (scale the queries of
+ * spx_edit_lookup with spx_edit_scale); the pipeline object.  (Tracks BELOW the key's rate -- labels, flags, feature rows -- are
+ * "EDIT LIST, ROW TRACKS" below.) */
 #define SPX_SAMPLES_INT16 0
 #define SPX_SAMPLES_FLOAT 1
 typedef struct { int64_t in_off, out_off, n_in, out_cap; int32_t channels, reserved; } spx_edit_master;
@@ -356,6 +356,69 @@ int spx_edit_replay_scaled(spx_plan_t plan, const spx_stream_job* jobs, int n_st
                            const int64_t* ops_cap, const int64_t* n_ops, const int64_t* n_out, const spx_edit_master* tracks,
                            int32_t p, int32_t q, int sample_format, const void* y_in, void* y_out, int64_t* n_out_y,
                            void* hip_stream);
+
+/* ---- EDIT LIST, ROW TRACKS: warp label and feature tracks to the output's time and back ----
+ * The companion a speech pipeline most often has sits BELOW the key's rate: phone or word labels at 100 Hz, VAD flags, filter-bank
+ * or pitch features at a 10 ms hop, 20 ms encoder frames of 768 floats, a per-frame loss mask.  spx_edit_warp_rows brings such a
+ * track from the INPUT's timeline onto the OUTPUT's (labels that fit the sped-up audio: speed augmentation with frame-level
+ * targets); spx_edit_unwarp_rows brings a track on the OUTPUT's timeline (posteriors, VAD or embeddings a model computed on the
+ * sped-up audio) back onto the INPUT's.  One search per row, whole rows moved; tests/edit_rows_ref.py states the definition below
+ * in Python integers and np.float32 scalars.
+ *
+ * A ROW TRACK has hop H >= 1 key frames per row and a phase 0 <= phase < H: row j describes key frames [j H, (j + 1) H), and frame
+ * j H + phase stands for it.  rows(x) = (x - phase + H - 1) / H for x > phase, else 0 -- the number of rows whose representative
+ * frame lies below x; spx_edit_rows returns it on the host (-1 for frames < 0, a hop outside 1 .. 2^20 or a phase outside
+ * [0, hop)).  A row has dim elements of elem_bytes (1, 2, 4 or 8) and is never interpreted outside BLEND mode; rows lie ld_in /
+ * ld_out >= dim elements apart, and elements at or behind column dim are never read and never written.
+ *
+ * L, n_out, the SOURCE of an output frame, forward and inverse are those of POSITION LOOKUP above; no = min(n_out[i],
+ * jobs[i].out_cap).  A ZERO ROW is dim elements of zero bytes.
+ *
+ * WARP (input time -> output time): stream i gets Ro = rows(no) rows.  For row j: u = j H + phase, k = the record that covers u
+ * (the largest k with out_at(k) <= u), t = u - out_at(k).
+ *   SPX_ROWS_NEAREST (any elem_bytes)   s = the source of the record at t; the row is input row s / H -- a zero row where s >= L
+ *                      (the replay's "a source frame at or behind L reads as 0"; likewise s < 0, which no job's list holds) or
+ *                      s / H >= the track's n_rows.
+ *   SPX_ROWS_BLEND   (elem_bytes 4, float32)   a copy record gives NEAREST.  A cross-fade has two sources, a + t and b + t, each a
+ *                      row (a + t) / H, (b + t) / H or a zero row by the same rule.  Where both are the same row (or both zero
+ *                      rows) the output is that row, bit for bit; otherwise, per element,
+ *                      ((ya * (float)(n - t)) + (yb * (float)t)) / (float)n: every operation rounded to float, no fused
+ *                      multiply-add, the division correctly rounded -- spx_edit_replay_scaled's float cross-fade; non-finite
+ *                      inputs give what IEEE arithmetic gives.
+ * UNWARP (output time -> input time, NEAREST only): stream i gets Ri = rows(L) rows, a number the host knows.  For row r:
+ * p = r H + phase, (o, k) = forward(p); the row is track row o / H -- a zero row where k = -1 (o = n_out: nothing at or behind p
+ * survives) or o / H >= the track's n_rows.  It needs the index spx_edit_index wrote.
+ *
+ *   jobs, ops, ops_cap, n_ops, n_out   exactly what spx_edit_lookup takes (n_ops, n_out: DEVICE -- nothing comes back to the host)
+ *   index    DEVICE what spx_edit_index wrote for these records (the unwarp only)
+ *   tracks   HOST   one per stream: in_off / out_off in ELEMENTS from y_in / y_out; n_rows = the rows the track has at in_off;
+ *            out_cap = the rows its region at out_off holds
+ *   y_in, y_out   DEVICE, aligned to elem_bytes only; the two do not overlap.  Rows move in 16-byte accesses where a row's source
+ *            and destination are aligned to 16, in the widest power of two they share otherwise
+ *   n_rows_out   DEVICE int64[n_streams], written by the call: the number of rows written; MINUS that number where it exceeds
+ *            tracks[i].out_cap, nothing written for that stream; 0, nothing written, for a stream with n_ops[i] <= 0 or
+ *            n_ops[i] > ops_cap[i], for a warp with n_out[i] <= 0, for an unwarp with n_out[i] < 0
+ * No stream disturbs another; whatever the records hold, nothing is read outside a track's n_rows rows or the stream's region of
+ * ops and index, and nothing is written outside the rows counted.  Asynchronous on hip_stream.  Refused with -1 and spx_last_error,
+ * nothing enqueued, the outputs untouched: everything spx_edit_lookup refuses; a NULL pointer (an unwarp without index says that it
+ * needs spx_edit_index); hop < 1 or above 2^20; phase outside [0, hop); dim < 1 or above 65536; a stride below dim or above 2^28; an
+ * elem_bytes outside the four; SPX_ROWS_BLEND with elem_bytes != 4; an unknown mode; a negative offset, n_rows or out_cap; y_in or
+ * y_out misaligned for the element.
+ * COST: one binary search per row in LDS and one pass over the rows' bytes (profiles/edit_rows.txt).
+ * OUT OF SCOPE: blending in the unwarp direction; rows behind a rate stage; a hop per stream; a pipeline-object form; lists from
+ * calls that record none; fractional row positions. */
+#define SPX_ROWS_NEAREST 0
+#define SPX_ROWS_BLEND 1
+typedef struct { int64_t in_off, out_off, n_rows, out_cap; } spx_edit_rows_track;   /* HOST: offsets in elements, counts in rows */
+int64_t spx_edit_rows(int64_t frames, int32_t hop, int32_t phase);
+int spx_edit_warp_rows(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const spx_edit_op* ops, const int64_t* ops_cap,
+                       const int64_t* n_ops, const int64_t* n_out, const spx_edit_rows_track* tracks, int32_t hop, int32_t phase,
+                       int32_t dim, int64_t ld_in, int64_t ld_out, int elem_bytes, int mode, const void* y_in, void* y_out,
+                       int64_t* n_rows_out, void* hip_stream);
+int spx_edit_unwarp_rows(spx_plan_t plan, const spx_stream_job* jobs, int n_streams, const spx_edit_op* ops, const int64_t* ops_cap,
+                         const int64_t* n_ops, const int64_t* n_out, const int32_t* index, const spx_edit_rows_track* tracks,
+                         int32_t hop, int32_t phase, int32_t dim, int64_t ld_in, int64_t ld_out, int elem_bytes, const void* y_in,
+                         void* y_out, int64_t* n_rows_out, void* hip_stream);
 
 /* ---- BATCH DTW: align pairs of feature sequences on the device -- cost, warp path and slopes per pair ----
  * The reference's perceptual check (TestSpeechSample, sonic_test.cc:639-724) aligns the spectrogram of the output to that of the
@@ -784,6 +847,9 @@ int spx_debug_last_replay_grid(int* launches);
 int spx_debug_last_edit_lookup_grid(int* launches);
 /* ... and the output blocks per stream of the last spx_edit_replay_scaled (4 096 values each, int16 or float), with its launches. */
 int spx_debug_last_scaled_grid(int* launches);
+/* ... and the row blocks per stream of the last spx_edit_warp_rows or spx_edit_unwarp_rows (at most spx_edit_lookup's choice, and
+ * no more than the longest stream can use: 64 rows a block where a row has more than 64 bytes, else 256), with its launches. */
+int spx_debug_last_rows_grid(int* launches);
 /* ... and the workgroups of the last spx_batch_dtw: one per pair, in each of its two launches (*launches = 2). */
 int spx_debug_last_dtw_grid(int* launches);
 int spx_timing_collect(double* sum_ms_analyze, double* sum_ms_walk, int* n_calls);

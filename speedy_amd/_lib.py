@@ -31,6 +31,10 @@ class EditMaster(C.Structure):  # spx_edit_master
                 ("channels", C.c_int32), ("reserved", C.c_int32)]
 
 
+class EditRowsTrack(C.Structure):  # spx_edit_rows_track
+    _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("n_rows", C.c_int64), ("out_cap", C.c_int64)]
+
+
 class DtwJob(C.Structure):  # spx_dtw_job
     _fields_ = [("a_off", C.c_int64), ("b_off", C.c_int64), ("path_off", C.c_int64), ("n_a", C.c_int32), ("n_b", C.c_int32)]
 
@@ -80,6 +84,13 @@ SYMBOLS = {
     "spx_edit_replay_scaled": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(EditMaster), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "spx_edit_rows": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "spx_edit_warp_rows": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(EditRowsTrack), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spx_edit_unwarp_rows": (C.c_int, [C.c_void_p, C.POINTER(StreamJob), C.c_int, C.c_void_p, c_int64_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(EditRowsTrack), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spx_dtw_workspace_bytes": (C.c_size_t, [C.POINTER(DtwJob), C.c_int, C.c_int]),
     "spx_batch_dtw": (C.c_int, [C.c_void_p, C.POINTER(DtwJob), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -126,6 +137,7 @@ SYMBOLS = {
     "spx_debug_last_replay_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_debug_last_edit_lookup_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_debug_last_scaled_grid": (C.c_int, [C.POINTER(C.c_int)]),
+    "spx_debug_last_rows_grid": (C.c_int, [C.POINTER(C.c_int)]),
     "spx_timing_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "spx_timing_last_tension_ms": (C.c_double, []),
     "spx_timing_last_rate_ms": (C.c_double, []),

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import EditMaster, EditTrack, StreamJob, Taps, lib
+from ._lib import EditMaster, EditRowsTrack, EditTrack, StreamJob, Taps, lib
 
 
 class Plan:
@@ -57,7 +57,9 @@ class Batch:
     GPU (spx_edit_replay), replay_scaled(tracks, channels, ratio) to masters at a higher sample rate, int16 or float32
     (spx_edit_replay_scaled).  The capacities are spx_plan_edit_ops' (ops_caps: one value or one per stream instead); not together
     with rate or time_map.  The plain call only.  locate(i, positions) and locate_all(positions) convert positions through the lists
-    to the sample (spx_edit_lookup), where lookup answers to 10 ms."""
+    to the sample (spx_edit_lookup), where lookup answers to 10 ms.  warp_rows(tracks, hop) brings label or feature rows on the
+    input's timeline onto the output's and unwarp_rows(tracks, hop) brings rows on the output's timeline back (spx_edit_warp_rows,
+    spx_edit_unwarp_rows)."""
 
     d_index = None          # the running maximum spx_edit_index writes, beside d_ops: made at the first forward locate
     _index_built = False    # ... and valid until the next run()
@@ -435,14 +437,8 @@ class Batch:
         d_rec = torch.zeros(d_q.numel(), dtype=torch.int32, device=self.device) if records else None
         L = self.plan.L
         hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
-        if not inverse and not self._index_built:
-            if self.d_index is None:
-                self.d_index = torch.zeros(max(1, self.op_offs[-1]), dtype=torch.int32, device=self.device)
-            rc = L.spx_edit_index(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
-                                  self.d_index.data_ptr(), hs)
-            if rc != 0:
-                raise RuntimeError("spx_edit_index: " + L.spx_last_error().decode())
-            self._index_built = True
+        if not inverse:
+            self._ensure_index(hs)
         rc = L.spx_edit_lookup(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
                                self.d_nout.data_ptr(), None if inverse else self.d_index.data_ptr(), d_off.data_ptr(), d_q.data_ptr(),
                                d_r.data_ptr(), d_rec.data_ptr() if records else None, 1 if inverse else 0, hs)
@@ -464,6 +460,91 @@ class Batch:
         empty = np.zeros(0, np.int64)
         got = self.locate_all([positions if k == i else empty for k in range(self.n)], inverse, records)
         return (got[0][i], got[1][i]) if records else got[i]
+
+    def _ensure_index(self, hs):
+        """The index of the last run's lists (spx_edit_index), built once per run()."""
+        L = self.plan.L
+        if self._index_built:
+            return
+        if self.d_index is None:
+            self.d_index = torch.zeros(max(1, self.op_offs[-1]), dtype=torch.int32, device=self.device)
+        rc = L.spx_edit_index(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
+                              self.d_index.data_ptr(), hs)
+        if rc != 0:
+            raise RuntimeError("spx_edit_index: " + L.spx_last_error().decode())
+        self._index_built = True
+
+    def _rows(self, tracks, hop, phase, blend, unwarp, stream):
+        if not self.with_edits:
+            raise ValueError("the batch was made without edits=True")
+        assert len(tracks) == self.n
+        hop = int(hop)
+        phase = hop // 2 if phase is None else int(phase)
+        ys = [np.ascontiguousarray(y.detach().cpu().numpy() if torch.is_tensor(y) else y) for y in tracks]
+        ys = [y.reshape(-1, 1) if y.ndim == 1 else y for y in ys]
+        kinds, dims = {y.dtype for y in ys}, {y.shape[1] for y in ys}
+        if len(kinds) != 1 or len(dims) != 1 or any(y.ndim != 2 for y in ys):
+            raise ValueError("the tracks of one call are (rows, dim) arrays of one dtype and one dim")
+        dtype, dim = next(iter(kinds)), int(next(iter(dims)))
+        if dtype.itemsize not in (1, 2, 4, 8) or dtype.kind not in "iufb":
+            raise ValueError("elements of 1, 2, 4 or 8 bytes, not %s" % dtype)
+        if blend and dtype != np.dtype(np.float32):
+            raise ValueError("blend=True takes float32 rows, not %s" % dtype)
+        L = self.plan.L
+        tr = (EditRowsTrack * self.n)()
+        in_off = out_off = 0
+        for i in range(self.n):
+            frames = self._row_limit(i) if unwarp else int(self.out_caps[i])
+            cap = L.spx_edit_rows(max(0, frames), hop, phase)
+            if cap < 0:
+                raise ValueError("spx_edit_rows refuses hop %d, phase %d" % (hop, phase))
+            tr[i].in_off, tr[i].out_off, tr[i].n_rows, tr[i].out_cap = in_off, out_off, ys[i].shape[0], cap
+            in_off += ys[i].size
+            out_off += cap * dim
+        bits = np.dtype("u%d" % dtype.itemsize)                  # the rows as bytes: torch has no uint16 / uint64 arithmetic to need
+        host = np.zeros(max(1, in_off), bits)
+        for i, y in enumerate(ys):
+            host[tr[i].in_off:tr[i].in_off + y.size] = y.view(bits).ravel()
+        d_y = torch.from_numpy(host.view(np.uint8)).to(self.device)
+        d_yout = torch.zeros(max(1, out_off) * dtype.itemsize, dtype=torch.uint8, device=self.device)
+        d_count = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        hs = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if unwarp:
+            self._ensure_index(hs)
+            rc = L.spx_edit_unwarp_rows(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
+                                        self.d_nout.data_ptr(), self.d_index.data_ptr(), tr, hop, phase, dim, dim, dim, dtype.itemsize,
+                                        d_y.data_ptr(), d_yout.data_ptr(), d_count.data_ptr(), hs)
+        else:
+            rc = L.spx_edit_warp_rows(self.plan.h, self.jobs, self.n, self.d_ops.data_ptr(), self._ops_cap_ptr(), self.d_nops.data_ptr(),
+                                      self.d_nout.data_ptr(), tr, hop, phase, dim, dim, dim, dtype.itemsize, 1 if blend else 0,
+                                      d_y.data_ptr(), d_yout.data_ptr(), d_count.data_ptr(), hs)
+        if rc != 0:
+            raise RuntimeError("%s: %s" % ("spx_edit_unwarp_rows" if unwarp else "spx_edit_warp_rows", L.spx_last_error().decode()))
+        torch.cuda.synchronize(self.device)
+        count = d_count.cpu().numpy()
+        if (count < 0).any():
+            raise RuntimeError("output capacity exceeded for streams %s" % np.nonzero(count < 0)[0][:8])
+        out = d_yout.cpu().numpy().view(dtype)
+        return [out[tr[i].out_off:tr[i].out_off + int(count[i]) * dim].reshape(-1, dim).copy() for i in range(self.n)]
+
+    def _row_limit(self, i):
+        """L of stream i: n_in for a linear job, (n_in // B) * B for a nonlinear one."""
+        n_in = int(self.lengths[i])
+        return n_in // self.plan.B * self.plan.B if self.jobs[i].nonlinear != 0.0 else n_in
+
+    def warp_rows(self, tracks, hop, phase=None, blend=False, stream=None):
+        """spx_edit_warp_rows over the whole batch: tracks[i] = a (rows, dim) numpy array or torch tensor on stream i's INPUT
+        timeline, one row per `hop` key frames (labels, flags, features; one dtype of 1, 2, 4 or 8 bytes and one dim per call; a
+        1-D array counts as dim 1), brought onto the OUTPUT timeline.  phase: the frame of a row that stands for it, hop // 2 by
+        default.  blend=True (float32): a row inside a cross-fade is the cross-fade of its two source rows.  Returns host numpy
+        arrays of spx_edit_rows(n_out) rows each."""
+        return self._rows(tracks, hop, phase, blend, False, stream)
+
+    def unwarp_rows(self, tracks, hop, phase=None, stream=None):
+        """spx_edit_unwarp_rows over the whole batch: tracks[i] on stream i's OUTPUT timeline (what a model computed on the sped-up
+        audio) brought back onto the INPUT timeline: spx_edit_rows(L) rows each, nearest row, zeros where nothing at or behind a
+        row survives.  The index is built at the first use after a run(), as locate_all builds it."""
+        return self._rows(tracks, hop, phase, False, True, stream)
 
     def tap_arrays(self, i):
         """tension/speed/features rows of stream i (host numpy)."""
